@@ -10,7 +10,12 @@ for integrated-rectifier maps).  value = N * D * steps / time, summed over ranks
 (weak scaling: every rank owns its own N-sample ensemble; the path has no
 data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C5|C2a|C2b|C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C5|C2a|C2b|C3] [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes what the last of the K timed steps computed - the forward map Z and the inverse X (in the
+standardised coordinates the device path works in), float64, one row per sample - at a fixed seeded sample of the
+ensemble (all of it when small) to DIR/forward_Z.npy and DIR/inverse_X.npy: the inputs are seeded, so two builds
+compare output for output.
 
 prints ONE JSON line (rank 0) with the `roofline` object of the dominant kernel - whichever of the two map
 kernels has the longer measured launch (today the table inverse; algorithmic bytes 8 N (d_used + D) forward,
@@ -87,6 +92,18 @@ def d_used(tm):
             else:
                 cols.update(int(e) for e in entry if not isinstance(e, str))
     return len(cols)
+
+
+DUMP_BYTES = 48 << 20       # --dump-outputs: what the sampled outputs may take in all (float64)
+
+
+def dump_sample_index(N, rows):
+    """Sorted sample indices of the outputs --dump-outputs writes: all N samples when they fit DUMP_BYTES (`rows` float64
+    values per sample over all dumped arrays), else a fixed seeded subset of at most 65 536 - the same in every run."""
+    n = min(N, 65536, DUMP_BYTES // (8 * rows))
+    if n >= N:
+        return np.arange(N, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(N, size=n, replace=False)).astype(np.int64)
 
 
 def _oracle_for(workload, n, seed):
@@ -660,8 +677,6 @@ def multi_gpu_extras(torch, dist, args, rank, world, backend):
     Never fatal for the headline line."""
     import ctypes
     from triangular_transport_toolbox_amd import comm, entf
-    if os.environ.get('TTM_BENCH_ABORT_IN_EXTRAS') == str(rank):          # (rehearsal of the guardian in main())
-        os.abort()
     out = {}
 
     def sync():
@@ -827,10 +842,15 @@ def main():
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='target duration of each CPU baseline leg')
     ap.add_argument('--extras-timeout', type=float, default=240.0,
                     help='N > 1: seconds the node-level extras may take before the headline line is printed without them')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (rank 0) to DIR/<name>.npy, float64, samples x components, '
+                         'at a fixed seeded sample of the ensemble (dump_sample_index)')
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return spawn_ranks(args)                 # (before anything touches the GPU)
     rank = int(os.environ.get('RANK', '0'))
@@ -959,6 +979,11 @@ def main():
         step()
     timed_first_step = n_steps_launched[0]
     elapsed = timed(step, args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # gathered on the device now: the measurements below overwrite Z and Xinv; written to disk at the end
+        idx = torch.from_numpy(dump_sample_index(N, D + d)).to(Z.device)
+        dumped = {'forward_Z': Z.index_select(1, idx), 'inverse_X': Xinv.index_select(1, idx)}
     # per-kernel timing with HIP events on the launch stream, directly behind the timed steps (same clock state)
     lib = tm._lib
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -1307,6 +1332,10 @@ def main():
         out.update(extra)
         if cpu is not None:
             out['cpu_baseline'] = cpu
+    if dumped is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), np.ascontiguousarray(t.cpu().numpy().T))
     if world > 1:
         # The node-level extras (strong scaling, the sample-sharded filter, the component-partitioned optimize()) are the
         # first code of this repository that runs RCCL collectives of its own over more than one rank: they run behind the

@@ -42,24 +42,17 @@ def test_no_fork_after_gpu_initialisation_in_bench():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('abort', [False, True])
-def test_two_rank_gloo_rehearsal_yields_one_json_line_with_the_node_level_keys(abort):
+def test_two_rank_gloo_rehearsal_yields_one_json_line_with_the_node_level_keys():
     """`bench.py --gpus 2 --backend gloo` on the one-GPU box: the never-GPU parent starts two ranks, rank 0's guardian
-    prints exactly one JSON line; its node-level keys are pinned here.  With TTM_BENCH_ABORT_IN_EXTRAS=0 rank 0 dies
-    inside the extras: still exactly one line (the headline, marked), and a non-zero exit code."""
-    env = dict(os.environ)
-    if abort:
-        env['TTM_BENCH_ABORT_IN_EXTRAS'] = '0'
+    prints exactly one JSON line; its node-level keys are pinned here.  (What the guardian prints when rank 0 dies is
+    checked above without a GPU.)"""
     res = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1',
                           '--n', '70001', '--prewarm-seconds', '0', '--no-optimize', '--extras-timeout', '400'],
-                         capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout[-2000:] + res.stderr[-2000:]
     js = json.loads(lines[0])
     assert js['n_gpus'] == 2 and js['config']['world_size'] == 2 and js['value'] > 0
-    if abort:
-        assert res.returncode != 0 and 'multi_gpu_extras_error' in js
-        return
     assert res.returncode == 0, res.stderr[-2000:]
     assert 'multi_gpu_extras_error' not in js
     assert 'rccl_ranks' in js                              # (None under gloo: the communicator is RCCL-only)
