@@ -12,8 +12,10 @@ import scipy.stats
 
 from tests.util import (ALL_CASES, INTEGRATED, SEPARABLE, case_X, coeff_lists, ctor_kwargs, load_case, make_oracle, relerr)
 
+EXAMPLES = ['ex02_partial', 'ex04_monod']          # examples 02 and 04 (make_golden.py ex02 ex04)
 
-@pytest.mark.parametrize('name', ALL_CASES)
+
+@pytest.mark.parametrize('name', ALL_CASES + EXAMPLES)
 def test_standardisation_and_special_terms(name):
     npz, desc = load_case(name)
     om = make_oracle(name, npz, desc)
@@ -32,7 +34,7 @@ def test_standardisation_and_special_terms(name):
     assert [len(c) for c in om.coeffs_nonmon] == desc['n_coeffs_nonmon']
 
 
-@pytest.mark.parametrize('name', ALL_CASES)
+@pytest.mark.parametrize('name', ALL_CASES + EXAMPLES)
 def test_basis_matrices(name):
     npz, desc = load_case(name)
     om = make_oracle(name, npz, desc)
@@ -48,7 +50,7 @@ def test_basis_matrices(name):
             assert relerr(om.der_fun_mon(k, Xs), npz['dPsi_mon_%d' % k]) < 1e-14
 
 
-@pytest.mark.parametrize('name', ALL_CASES)
+@pytest.mark.parametrize('name', ALL_CASES + EXAMPLES)
 def test_forward_map(name):
     npz, desc = load_case(name)
     om = make_oracle(name, npz, desc)
@@ -98,6 +100,53 @@ def test_example01_known_answer():
     Z = om.map(npz['X_head'])
     assert relerr(Z, npz['Z_head']) < 1e-13
     assert relerr(om.inverse_map(npz['inv_Z']), npz['inv_X']) < 1e-9
+
+
+def test_example02_partial_map():
+    """example_02.py: the order-10 second spiral component alone at the shipped coefficients, its conditional inverses at
+    X_star = 0.6 and SciPy's BFGS from there."""
+    npz, desc = load_case('ex02_partial')
+    om = make_oracle('ex02_partial', npz, desc)
+    X = case_X('ex02_partial', npz)
+    Z = om.map(X)
+    assert relerr(Z[:512], npz['Z']) < 1e-13
+    assert relerr(Z.mean(0), npz['Z_mean']) < 1e-13 and relerr(Z.std(0), npz['Z_std']) < 1e-13
+    div = len(om.coeffs_nonmon[0])
+    assert abs(om.objective_function(None, 0, div) - npz['J'][0]) <= 1e-13 * (1 + abs(npz['J'][0]))
+    assert relerr(om.objective_function_jacobian(None, 0, div), npz['G_0']) < 1e-12
+    assert relerr(om.inverse_map(npz['inv_Z'], X_star=npz['inv_Xstar']), npz['inv_X']) < 1e-8
+    assert relerr(om.inverse_map(Z[:256], X_star=npz['inv_Xstar']), npz['inv_map_X']) < 1e-8
+    om.optimize()
+    assert relerr(om.coeffs_mon[0], npz['opt_coeffs_mon_0']) < 1e-6
+    assert relerr(om.coeffs_nonmon[0], npz['opt_coeffs_nonmon_0']) < 1e-6
+
+
+def test_example04_monod():
+    """example_04.py: the separable map of (r_max, K) behind 20 observed rates - reduced problems, optimum, map and the
+    two conditional inverses (X_star of varying rows; the observations on every row)."""
+    npz, desc = load_case('ex04_monod')
+    om = make_oracle('ex04_monod', npz, desc)
+    for k in range(om.D):
+        A, aux = om.separable_setup(k)
+        assert relerr(A, npz['sep_A_%d' % k]) < 1e-12
+        for c, J, G in zip(npz['sep_c_%d' % k], npz['sep_J_%d' % k], npz['sep_G_%d' % k]):
+            Jo, Go = om.separable_objective(c.copy(), npz['sep_A_%d' % k], k)
+            assert abs(Jo - J) <= 1e-13 * (1 + abs(J))
+            assert relerr(Go, G) < 1e-12
+        Jo, Go = om.separable_objective(npz['coeffs_mon_%d' % k].copy(), npz['sep_A_%d' % k], k)
+        assert abs(Jo - npz['sep_Jopt_%d' % k]) <= 1e-13 * (1 + abs(Jo)) and relerr(Go, npz['sep_Gopt_%d' % k]) < 1e-12
+        assert relerr(om.separable_nonmonotone(npz['coeffs_mon_%d' % k], aux), npz['coeffs_nonmon_%d' % k]) < 1e-9
+    assert relerr(om.map(npz['X']), npz['Z']) < 1e-13
+    assert relerr(om.inverse_map(npz['inv_Z'], X_star=npz['inv_Xstar']), npz['inv_X']) < 1e-11
+    Xstar = np.repeat(npz['obs'][None, :], len(npz['X']), axis=0)
+    assert relerr(om.inverse_map(npz['Z'], X_star=Xstar), npz['inv_obs_X']) < 1e-11
+    ref_mon, ref_non = coeff_lists(npz, om.D)
+    om.coeffs_mon = [c * 0 for c in ref_mon]
+    om.coeffs_nonmon = [c * 0 for c in ref_non]
+    om.optimize()
+    for k in range(om.D):
+        assert relerr(om.coeffs_mon[k], ref_mon[k]) < 1e-6
+        assert relerr(om.coeffs_nonmon[k], ref_non[k]) < 1e-6
 
 
 @pytest.mark.parametrize('name', ['c1_int', 'c2a_int', 'c3_int', 'c5_int'])

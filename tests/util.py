@@ -29,7 +29,7 @@ def case_X(name, npz):
     from triangular_transport_toolbox_amd import specs
     if name == 'c5_sep':
         return specs.sample_mixture(int(npz['N']))
-    if name == 'ex01_order10':
+    if name in ('ex01_order10', 'ex02_partial'):
         return specs.sample_spiral(int(npz['N']), seed=0)
     raise KeyError(name)
 

@@ -1496,7 +1496,7 @@ class transport_map():
                                               else int(self._cm.n_nm[k]))
         work = self._workspace(self._lib.ttm_reduce_work_size(nout))
         coef_k = np.ascontiguousarray(coef_k, dtype=float)
-        if self._dist() is None and len(coef_k) <= HOSTCOEF_MAX:
+        if self._coefficients_as_arguments(len(coef_k)):
             # host-driven optimiser: coefficients as kernel arguments, result written to pinned host memory,
             # one stream synchronisation per evaluation (no H2D / D2H copies, two launches)
             torch = _torch()
@@ -1509,6 +1509,11 @@ class transport_map():
                                             self._N, self._ptr(work), self._ptr(out), self._stream()))
         self._allreduce(out)
         return out.cpu().numpy()
+
+    def _coefficients_as_arguments(self, m):
+        """True when an objective evaluation of a component with m coefficients passes them as kernel arguments
+        (ttm_objective_host, results in pinned host memory); False: they go to the device first (ttm_objective)."""
+        return self._dist() is None and m <= HOSTCOEF_MAX
 
     def _objective_launch(self, k, coef_k, work=None):
         """The launches of one objective + gradient evaluation of component k (ttm_objective_host: sums into pinned host
@@ -2195,15 +2200,16 @@ class transport_map():
                 dpsi = dpsi_keep[k] if direct[k] is None else None
                 vec = host_keep['vec'].get(k)
                 if vec is None or vec[0].shape != (m, m):
-                    vec = host_keep['vec'][k] = (np.empty((m, m)), np.empty(m), np.empty(m),
-                                                 np.array([-np.inf if v is None else v for v in self.optimization_constraints_lb[k]], dtype=float),
-                                                 np.array([np.inf if v is None else v for v in self.optimization_constraints_ub[k]], dtype=float))
+                    vec = host_keep['vec'][k] = (np.empty((m, m)), np.empty(m), np.empty(m), np.empty(m), np.empty(m))
                     fresh = True
                 Ab, b, x, lb, ub = vec
                 Ab[...] = A
                 A = Ab
                 b[...] = self.delta * np.sum(A, axis=-1)
                 x[...] = self.coeffs_mon[k]
+                # (the bounds are public attributes the caller may have edited since the last call, as TM:3102 reads them)
+                lb[...] = [-np.inf if v is None else v for v in self.optimization_constraints_lb[k]]
+                ub[...] = [np.inf if v is None else v for v in self.optimization_constraints_ub[k]]
                 keep.append((A, b, x, lb, ub, dpsi, solve_nonmon))
                 t = tasks[i]
                 if not fresh and direct[k] is None:
