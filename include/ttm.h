@@ -12,7 +12,10 @@
  * Conventions
  *  - plain C types only; all array arguments are DEVICE pointers unless the
  *    name starts with h_ (host); the caller owns every buffer (PyTorch-ROCm is
- *    the allocator in the Python host, any hipMalloc'ed memory works);
+ *    the allocator in the Python host, any hipMalloc'ed memory works) - with
+ *    ONE exception: the library allocates, once per process, the 16 KB of
+ *    fine-grained device memory its mailboxes come from (ttm_mailbox_acquire;
+ *    the evaluation servers of ttm_optimize_separable) and keeps it;
  *  - `stream` is a hipStream_t passed as void* (NULL = default stream); no entry
  *    point synchronises, allocates or frees: all are graph-capturable;
  *  - every function returns 0 on success, a negative TTM_E_* code otherwise;
@@ -588,10 +591,10 @@ int ttm_objective_sep_direct_sent(const double* xk, int64_t N, int32_t m, const 
  * loop - resident workgroups poll a mailbox in fine-grained DEVICE memory that the host writes through the PCIe BAR (posted
  * writes: 2.6-3.7 us per request against 6.2 us for a launch + completion round trip, tools/micro/mailbox.cpp) and answer every
  * request the way ttm_objective_sep_cached_sent does (the same bits).  ttm_mailbox_acquire: a 256-byte mailbox of the library's
- * pool (NULL: none - launch per evaluation); the host writes the m trial coefficients to box + 8, then (sfence) the word
- * gen << 32 | request number to box, request numbers 1, 2, ...; gen << 32 | 0xffffffff ends the server; a server that is not
- * asked anything for 0.2 s leaves by itself.  work / out_host as ttm_objective_sep_cached_sent (rows armed by ttm_sentinel_fill).
- * TTM_E_UNSUPPORTED: larger grids, option sep_server = 0.                                                                */
+ * pool (NULL: none - all in use, or a device without a large BAR - launch per evaluation); the host writes the m trial
+ * coefficients to box + 8, then (sfence) the word gen << 32 | request number to box, request numbers 1, 2, ...;
+ * gen << 32 | 0xffffffff ends the server; a server that is not asked anything for 0.2 s leaves by itself.  work / out_host as
+ * ttm_objective_sep_cached_sent (rows armed by ttm_sentinel_fill).  TTM_E_UNSUPPORTED: larger grids, option sep_server = 0. */
 void* ttm_mailbox_acquire(void);
 void ttm_mailbox_release(void* box);
 int ttm_objective_sep_server_start(const double* dPsi, int64_t ldp, int64_t N, int32_t m, double delta, double* work,
@@ -695,8 +698,10 @@ typedef struct ttm_sep_task {
     const double* xk;            /* device, the component's x_k column (N doubles) */
     const int32_t* kinds;        /* device, m */
     const double* pars;          /* device, 5 m */
-    int32_t armed;               /* in: 1 = the rows of partial sums in `work` are armed (ttm_sentinel_fill) for this m and N - a
-                                    previous call on the same `work` left them so; out: 1 when this call leaves them armed   */
+    int32_t armed;               /* opaque layout key of the rows of partial sums in `work`: in: what a previous call on the same
+                                    `work` wrote back (0: none - the rows are armed anew, ttm_sentinel_fill); out: the key this
+                                    call leaves them armed under, 0 when it leaves them unarmed.  A key that does not match the
+                                    task's m, N and the current options is ignored.                                          */
 } ttm_sep_task;
 /* ttm_separable_reduce_l2 (host arithmetic only): the reduced separable problem with L2 regularisation (TM:3021-3050,
  * 3148-3169) from the (n + m) x (n + m) Gram matrix G of [Psi_nonmon | Psi_mon] (row-major, host): A (m x m) and sol (n x m,

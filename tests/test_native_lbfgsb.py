@@ -135,3 +135,93 @@ def test_native_l2_reduction_equals_the_numpy_path():
         G = -np.identity(3)
         A, S = np.empty((1, 1)), np.empty((2, 1))
         assert lib.ttm_separable_reduce_l2(ctypes.c_void_p(G.ctypes.data), 2, 1, 0.05, ctypes.c_void_p(A.ctypes.data), ctypes.c_void_p(S.ctypes.data)) != 0
+
+
+class SepTask:
+    """One component problem of the separable entry points on host buffers (the test double's pointers are host pointers)."""
+
+    def __init__(self, seed, m, N=400):
+        rng = np.random.default_rng(seed)
+        x = rng.standard_normal(N)
+        cols = [np.exp(-0.5 * ((x - c) / 0.7) ** 2) for c in np.linspace(-1.0, 1.0, m)]
+        self.m, self.N = m, N
+        self.dpsi = np.ascontiguousarray(np.stack(cols) + 0.05)       # m rows of N doubles, positive
+        B = rng.standard_normal((m + 3, m))
+        self.A = np.ascontiguousarray(B.T @ B / (m + 3) + 0.5 * np.eye(m))
+        self.b = 1e-8 * self.A.sum(axis=1)
+        self.lb, self.ub = np.zeros(m), np.full(m, np.inf)
+        self.x = np.full(m, 0.7)
+        self.work = np.zeros(4096)
+        self.counter = np.zeros(16, dtype=np.uint32)
+        self.sums = np.zeros(2 + m + 8)
+        self.result = np.zeros(5)
+
+    def fill(self, t, null=None, m=None):
+        p = lambda a: None if a is None else a.ctypes.data                  # noqa: E731
+        for name, arr in (('dPsi', self.dpsi), ('A', self.A), ('b', self.b), ('lb', self.lb), ('ub', self.ub), ('x', self.x),
+                          ('work', self.work), ('counter', self.counter), ('sums_host', self.sums)):
+            setattr(t, name, None if name == null else p(arr))
+        t.ldp, t.m, t.rc, t.armed = self.N, self.m if m is None else m, 0, 0
+        return t
+
+    def single(self, lib, null=None, m=None):
+        p = lambda name, a: None if name == null else a.ctypes.data          # noqa: E731
+        return lib.ttm_optimize_separable(p('dPsi', self.dpsi), self.N, self.N, self.m if m is None else m, p('A', self.A), p('b', self.b),
+                                          float(self.N), 1e-8, p('lb', self.lb), p('ub', self.ub), p('x', self.x), p('work', self.work),
+                                          p('counter', self.counter), None, p('sums_host', self.sums), None, None, 0, self.result.ctypes.data)
+
+
+def run_batch(lib, probs, nthreads=2, null=None, m=None, bad=None):
+    """ttm_optimize_separable_batch over `probs`; task `bad` gets `null` as its NULL pointer / `m` as its term count."""
+    tasks = (_capi.ttm_sep_task * len(probs))()
+    for i, pr in enumerate(probs):
+        pr.fill(tasks[i], null if i == bad else None, m if i == bad else None)
+    rc = lib.ttm_optimize_separable_batch(tasks, len(probs), probs[0].N, float(probs[0].N), 1e-8, nthreads, None, 0)
+    return rc, tasks
+
+
+@pytest.mark.parametrize('null', ['dPsi', 'A', 'b', 'x', 'work', 'counter', 'sums_host', None])
+def test_separable_entry_points_check_their_tasks(null):
+    """ttm_optimize_separable, the threaded batch and the batch that launches the one-term components' first evaluations ahead
+    (the filter's shape: two components with one monotone term and one other) check every task before anything is launched or
+    indexed: TTM_E_ARG (-1) for a NULL pointer and for m = 0, TTM_E_LIMIT (-3) for m = 17; a task that is refused keeps its x."""
+    from tests.hostemu import emu
+    lib = emu.lib()
+    cases = [(-1, null, None)] if null else [(-1, None, 0), (-3, None, 17)]
+    for want, nul, m in cases:
+        pr = SepTask(0, 17 if m == 17 else 3)
+        assert pr.single(lib, nul, m) == want
+        assert np.all(pr.x == 0.7)
+        if nul == 'dPsi':
+            continue                                      # (a batch task without dPsi reads the x_k column: tested below)
+        big = SepTask(5, 17) if m == 17 else SepTask(5, 3)
+        for probs, bad in (([SepTask(1, 3), SepTask(2, 4), big], 2),                  # threaded
+                           ([SepTask(3, 1), SepTask(4, 1), big], 2)):                 # one-term components launched ahead
+            rc, tasks = run_batch(lib, probs, null=nul, m=m, bad=bad)
+            assert rc == want and tasks[bad].rc == want
+            assert np.all(probs[bad].x == 0.7)
+            assert all(tasks[i].rc == 0 for i in range(len(probs)) if i != bad)
+    # a batch task without dPsi needs the x_k column, its kinds and constants
+    rc, tasks = run_batch(emu.lib(), [SepTask(3, 1), SepTask(4, 1), SepTask(5, 3)], null='dPsi', bad=2)
+    assert rc == -1 and tasks[2].rc == -1
+
+
+def test_batch_that_launches_ahead_equals_the_threaded_batch():
+    """The filter-shaped batch (two one-term components and one other: no threads, the one-term components' first evaluations
+    launched ahead) gives the coefficients of the threaded batch (a second other component in the batch) and of
+    ttm_optimize_separable component by component, bit for bit."""
+    from tests.hostemu import emu
+    lib = emu.lib()
+    mk = lambda: [SepTask(11, 1), SepTask(12, 1), SepTask(13, 4)]         # noqa: E731
+    ahead = mk()
+    rc, _ = run_batch(lib, ahead, nthreads=1)
+    assert rc == 0
+    threaded = mk() + [SepTask(14, 3)]
+    rc, _ = run_batch(lib, threaded, nthreads=3)
+    assert rc == 0
+    single = mk()
+    for pr in single:
+        assert pr.single(lib) == 0
+    for a, t, s in zip(ahead, threaded, single):
+        assert np.array_equal(a.x, t.x) and np.array_equal(a.x, s.x)
+        assert not np.all(a.x == 0.7)

@@ -486,6 +486,55 @@ def test_an_evaluation_server_that_was_left_waiting_is_replaced(tmp_path):
     assert np.array_equal(out['plain'], out['stalled'])
 
 
+@pytest.mark.gpu
+def test_a_single_component_loop_runs_on_the_evaluation_server(ttm_opt):
+    """ttm_optimize_separable on a component of the c3_sep case (five monotone terms, a grid of at most 128 workgroups) answers its
+    whole loop with ONE launch of k_objective_sep_server - the last kernel it launches - and finds the coefficients of a launch per
+    evaluation (option sep_server = 0), bit for bit."""
+    import ctypes
+    npz, desc = load_case('c3_sep')
+    tm = make_tm('c3_sep', npz, desc, with_coeffs=False)
+    tm.optimizer_threads = 1
+    k = 1
+    assert int(tm._cm.n_mon[k]) > 1
+    tm._lib.ttm_last_kernel.restype = ctypes.c_char_p
+    A, _ = tm.separable_setup(k)
+    bounds = list(zip(tm.optimization_constraints_lb[k], tm.optimization_constraints_ub[k]))
+    got = {}
+    for opt in (-1, 0):
+        ttm_opt('sep_server', opt)
+        tm._sep_cache_begin(k)
+        res = tm._optimize_separable_native(A, k, np.asarray(tm.coeffs_mon[k], dtype=float), bounds)
+        got[opt] = (res.x, tm._lib.ttm_last_kernel().decode())
+        tm._sep_cache_end()
+    assert got[-1][1] == 'k_objective_sep_server'
+    assert got[0][1] == 'k_objective_sep_cached'
+    assert np.array_equal(got[-1][0], got[0][0])
+
+
+@pytest.mark.gpu
+def test_rows_armed_under_another_setting_are_not_trusted(ttm_opt):
+    """The optimiser batch remembers how it left the rows of partial sums of each component (ttm_sep_task.armed: a key of the grid and
+    the term count).  After option sep_sentinel = 0 the next optimize() on the same map takes the ticket finish - it leaves no rows
+    armed - instead of trusting the key of the previous run, and finds the coefficients of a fresh map, bit for bit."""
+    npz, desc = load_case('c3_sep')
+    tm = make_tm('c3_sep', npz, desc, with_coeffs=False)
+    tm.optimize()
+    first = [np.array(c) for c in tm.coeffs_mon + tm.coeffs_nonmon]
+    armed = tm._sep_batch_scratch[6]
+    assert armed and all(v != 0 for v in armed.values())
+    ttm_opt('sep_sentinel', 0)
+    for k in range(tm.D):
+        tm.coeffs_mon[k] = np.asarray(tm.coeffs_mon[k], dtype=float) * 0 + tm.coeffs_init
+        tm.coeffs_nonmon[k] = np.asarray(tm.coeffs_nonmon[k], dtype=float) * 0 + tm.coeffs_init
+    tm.optimize()
+    assert tm._sep_batch_scratch[6] is armed and all(v == 0 for v in armed.values())
+    fresh = make_tm('c3_sep', npz, desc, with_coeffs=False)
+    fresh.optimize()
+    for a, b, c in zip(tm.coeffs_mon + tm.coeffs_nonmon, fresh.coeffs_mon + fresh.coeffs_nonmon, first):
+        assert np.array_equal(a, b) and np.array_equal(a, c)
+
+
 def test_ents_backward_smoother_matches_reference(backend):
     """Ensemble Transport Smoother (example_07.py:368-465): the 6-column block map (skip_dimensions = 3, probabilist's
     Hermite polynomials with 'HF' terms, L2), three backward steps of reset -> optimize -> map -> inverse_map with

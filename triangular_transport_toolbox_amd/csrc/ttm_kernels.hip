@@ -19,8 +19,6 @@
 
 #include <hip/hip_runtime.h>
 #include <mutex>
-#include <setjmp.h>
-#include <signal.h>
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -4017,11 +4015,19 @@ int ttm_objective_sep_cached_marked(const double* dPsi, int64_t ldp, int64_t N, 
     return launch_sep_objective(dPsi, ldp, nullptr, nullptr, nullptr, N, m, h_coef_mon, delta, work, counter, out, flag, mark, false, stream);
 }
 
+// The layout of the armed rows of partial sums for m monotone terms over N samples (internal to csrc/ttm_optim.cpp, not exported):
+// 0 when the self-validating sums do not apply (option sep_sentinel = 0, a grid of more than TTM_SENT_WGS workgroups), else a key
+// of the grid and m - rows armed under one key are armed for every (m, N) with the same key.
+extern "C" __attribute__((visibility("hidden"))) int sentinel_layout(int32_t m, int64_t N) {
+    if (m < 1 || m > TTM_SEPC_MAXM || N < 1 || tuning().sep_sentinel == 0) return 0;
+    const int nb = grid_for(N, 256 * 4);
+    return nb > TTM_SENT_WGS ? 0 : nb << 8 | m;
+}
+
 int ttm_sentinel_fill(double* work, int32_t m, int64_t N, void* stream) {
     if (!work || m < 1 || m > TTM_SEPC_MAXM || N < 1) return set_err(TTM_E_ARG, "ttm_sentinel_fill: bad arguments%s");
-    const int nb = grid_for(N, 256 * 4);
-    if (nb > TTM_SENT_WGS || tuning().sep_sentinel == 0) return TTM_E_UNSUPPORTED;
-    const int n = 2 * nb * (1 + m);                   // (two regions: the evaluation server alternates between them)
+    if (!sentinel_layout(m, N)) return TTM_E_UNSUPPORTED;
+    const int n = 2 * grid_for(N, 256 * 4) * (1 + m);  // (two regions: the evaluation server alternates between them)
     hipLaunchKernelGGL(k_fill_bits, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)(work + TTM_OBJ_FOLD_MAX), n,
                        (unsigned long long)TTM_SENT_BITS);
     return check_launch("k_fill_bits");
@@ -4047,39 +4053,21 @@ int ttm_objective_sep_server_start(const double* dPsi, int64_t ldp, int64_t N, i
 }
 
 // Mailboxes of the evaluation servers: 256-byte slots of ONE fine-grained device allocation per process (host-writable through the
-// PCIe BAR; hipExtMallocWithFlags), handed out and taken back under a lock.  NULL: none to be had (no such memory on this
-// platform, or all 64 in use) - the caller launches per evaluation.
+// PCIe BAR; hipExtMallocWithFlags), handed out and taken back under a lock - the one buffer the library owns.  NULL: none to be had
+// (all 64 in use, or a device without a large BAR: the host cannot store into its memory) - the caller launches per evaluation.
 static std::mutex g_box_lock;
 static unsigned char* g_box_pool = nullptr;
 static unsigned long long g_box_used = 0;
 static bool g_box_tried = false;
-static sigjmp_buf g_box_jmp;
-static void box_fault(int) { siglongjmp(g_box_jmp, 1); }
 void* ttm_mailbox_acquire(void) {
     std::lock_guard<std::mutex> g(g_box_lock);
     if (!g_box_tried) {
         g_box_tried = true;
+        int dev = 0, large_bar = 0;
         void* p = nullptr;
-        if (hipExtMallocWithFlags(&p, 64 * 256, hipDeviceMallocFinegrained) == hipSuccess && p) {
-            bool ok = hipMemset(p, 0, 64 * 256) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-            if (ok) {
-                // the one thing the servers need from the platform: a HOST store into this memory (a system without a large PCIe
-                // BAR maps none of it).  Probed once, with the fault caught: no mailboxes then, a launch per evaluation.
-                struct sigaction sa, old_segv, old_bus;
-                memset(&sa, 0, sizeof(sa));
-                sa.sa_handler = box_fault;
-                sigemptyset(&sa.sa_mask);
-                sigaction(SIGSEGV, &sa, &old_segv);
-                sigaction(SIGBUS, &sa, &old_bus);
-                ok = false;
-                if (sigsetjmp(g_box_jmp, 1) == 0) {
-                    *(volatile unsigned long long*)p = 0ull;
-                    ok = true;
-                }
-                sigaction(SIGSEGV, &old_segv, nullptr);
-                sigaction(SIGBUS, &old_bus, nullptr);
-            }
-            if (ok) g_box_pool = (unsigned char*)p;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess &&
+            large_bar == 1 && hipExtMallocWithFlags(&p, 64 * 256, hipDeviceMallocFinegrained) == hipSuccess && p) {
+            if (hipMemset(p, 0, 64 * 256) == hipSuccess && hipDeviceSynchronize() == hipSuccess) g_box_pool = (unsigned char*)p;
             else (void)hipFree(p);
         }
         (void)hipGetLastError();

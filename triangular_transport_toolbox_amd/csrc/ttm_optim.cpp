@@ -29,6 +29,12 @@
 #include "ttm_bfgs.h"
 #include "ttm_lbfgsb.h"
 
+#ifndef TTM_HOST_ONLY  // the layout key of the armed rows of partial sums, 0: none for m, N (csrc/ttm_kernels.hip; not exported)
+extern "C" int sentinel_layout(int32_t m, int64_t N);
+#else                  // (the host double has no self-validating sums: its loops take the marked call)
+static int sentinel_layout(int32_t, int64_t) { return 0; }
+#endif
+
 namespace {
 
 #ifndef TTM_HOST_ONLY
@@ -55,15 +61,16 @@ int poll_mark(const double* flag_, double mark, void* stream) {
 // The self-validating results of ttm_objective_sep_cached_sent: the host fills the n slots with a bit pattern no arithmetic
 // produces (arm_values), the finishing workgroup overwrites each slot with one 8-byte store, and the slots are polled until
 // none holds the pattern - no completion mark, no drain on the device in front of it.  TTM_E_HIP: the stream went idle or
-// failed without results, or the device gave up waiting for its own workgroups (the FAIL pattern).
+// failed without results, or the device gave up waiting for its own workgroups (the FAIL pattern); *retry (nullable): true for
+// the idle stream and the FAIL pattern - nobody is going to answer, but the stream itself has not failed.
 const uint64_t kSentBits = 0x7FF4DEADBEEF0001ull, kSentFail = 0x7FF4DEADBEEF0002ull;
 void arm_values(double* v_, int n) {
     std::atomic<uint64_t>* v = reinterpret_cast<std::atomic<uint64_t>*>(v_);
     for (int i = 0; i < n; ++i) v[i].store(kSentBits, std::memory_order_relaxed);
     std::atomic_thread_fence(std::memory_order_release);
 }
-int poll_values(const double* v_, int n, void* stream, bool* unanswered = nullptr) {
-    if (unanswered) *unanswered = false;
+int poll_values(const double* v_, int n, void* stream, bool* retry = nullptr) {
+    if (retry) *retry = false;
     const std::atomic<uint64_t>* v = reinterpret_cast<const std::atomic<uint64_t>*>(v_);
     static_assert(sizeof(std::atomic<uint64_t>) == sizeof(double), "lock-free 64-bit atomics expected");
     auto pending = [&]() {
@@ -78,7 +85,7 @@ int poll_values(const double* v_, int n, void* stream, bool* unanswered = nullpt
         if (st == hipErrorNotReady) continue;
         if (st == hipSuccess) (void)hipStreamSynchronize((hipStream_t)stream);
         if (pending()) {
-            if (unanswered) *unanswered = st == hipSuccess;      // (an idle stream and no results: nobody is going to answer)
+            if (retry) *retry = st == hipSuccess;
             return TTM_E_HIP;
         }
 #else
@@ -88,7 +95,10 @@ int poll_values(const double* v_, int n, void* stream, bool* unanswered = nullpt
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     for (int i = 0; i < n; ++i)
-        if (v[i].load(std::memory_order_relaxed) == kSentFail) return TTM_E_HIP;
+        if (v[i].load(std::memory_order_relaxed) == kSentFail) {
+            if (retry) *retry = true;
+            return TTM_E_HIP;
+        }
     return TTM_OK;
 }
 
@@ -105,6 +115,19 @@ int wait_for_mark(double* flag_, long& seq, void* stream) {
     return TTM_OK;
 #endif
 }
+
+// the stream calls of the separable loops (the host double has no streams: its work is done when a call returns)
+#ifndef TTM_HOST_ONLY
+void store_fence() { _mm_sfence(); }
+int stream_idle(void* stream) { return hipStreamSynchronize((hipStream_t)stream) == hipSuccess ? TTM_OK : TTM_E_HIP; }
+int copy_to_host(double* dst, const double* src, int n, void* stream) {
+    return hipMemcpyAsync(dst, src, (size_t)n * 8, hipMemcpyDeviceToHost, (hipStream_t)stream) == hipSuccess ? TTM_OK : TTM_E_HIP;
+}
+#else
+void store_fence() { std::atomic_thread_fence(std::memory_order_seq_cst); }
+int stream_idle(void*) { return TTM_OK; }
+int copy_to_host(double* dst, const double* src, int n, void*) { memcpy(dst, src, (size_t)n * 8); return TTM_OK; }
+#endif
 
 // Independent component problems side by side (the reference's process pool over components, TM:2789-2845): worker
 // threads draw tasks from a shared counter; each worker owns one HIP stream, so the reductions of different components
@@ -222,208 +245,198 @@ int ttm_lbfgsb_minimize(int32_t n, double* x, const double* lb, const double* ub
 
 namespace {
 
-// the reduced separable problem of one component (TM:2978-3018) minimised by the L-BFGS-B loop; launch(cc, out, flag,
-// mark, stream) enqueues the reduction of the sums for coefficients cc into out (flag != NULL: with the completion mark)
-//
-// ONE monotone term (m = 1: the filtering and smoothing maps of Examples C, most components of Markov-type maps): the sample
-// sums are known in closed form once they have been taken at one point.  dS_n = dPsi_n c + delta dPsi_n = dPsi_n (c + delta)
-// (TM:2990-2993), so sum_n log dS_n = N log(c + delta) + sum_n log dPsi_n and sum_n dPsi_n / dS_n = N / (c + delta): the
-// first evaluation of the loop goes to the device, every later one is two host operations - the same function to
-// rounding (1e-16 relative, like the order of a reduction), no launch, no round trip.  `delta` < 0 switches it off.
-typedef int (*SentLaunch)(const double* cc, double* out_host, void* stream, void* user);
-
-// what the evaluation server of a loop needs (ttm_objective_sep_server_start; cached derivative basis only)
-struct ServerArgs { const double* dPsi; int64_t ldp, N; int32_t m; double delta; double* work; };
-std::atomic<uint32_t> g_server_gen{0};
-
-template <class Launch>
-int optimize_separable_with(Launch launch, int32_t m, const double* A, const double* b, double Ntotal, const double* lb,
-                            const double* ub, double* x, double* sums_dev, double* sums_host, ttm_comm* comm, void* stream,
-                            int32_t maxiter, double* result, double delta = -1.0, SentLaunch sent = nullptr, void* sent_user = nullptr,
-                            const double* pre_x = nullptr, const ServerArgs* server = nullptr) {
-    struct Ctx {
-        Launch& launch;
-        const double *A, *b;
-        double invN;
-        double *sums_dev, *sums_host;
-        ttm_comm* comm;
-        void* stream;
-        int rc;
-        long seq;
-        double delta, Nw, KN;                                // closed form of m = 1: weights N, sum_n log dPsi_n
-        bool closed, have0;
-        SentLaunch sent;                                     // the evaluation with self-validating results (no ticket, no mark)
-        void* sent_user;
-        const double* pre_x;                                 // an evaluation at this point is in flight already (its results
-        const ServerArgs* server;                            // arrive in sums_host, armed); ONE launch answers every evaluation of the loop
-        unsigned char* box;                                  //   its mailbox (fine-grained device memory, host-written), once it runs
-        uint32_t gen, round;
-    } c{launch, A, b, 1.0 / Ntotal, sums_dev, sums_host, comm, stream, 0, 0, delta, 0.0, 0.0,
-        m == 1 && delta >= 0.0 && lb && lb[0] >= 0.0, false, comm ? nullptr : sent, sent_user, (sent && !comm) ? pre_x : nullptr,
-        (sent && !comm && m > 1) ? server : nullptr, nullptr, 0, 0};
-    if (!c.pre_x) sums_host[1 + m] = 0.0;                    // the completion mark (sums_host: >= 2 + m doubles)
-    auto fun = [](int32_t n, const double* cc, double* f, double* g, void* user) -> int32_t {
-        Ctx& c = *(Ctx*)user;
-        // sums[0] = sum_n log dS_n, sums[1 + i] = sum_n dPsi_{n,i} / dS_n  (TM:2990-3006), over the local samples
-        double* out = c.comm ? c.sums_dev : c.sums_host;
-        bool have = false;
-        if (c.pre_x) {                                       // the evaluation that was launched ahead: wait for it whatever it is good for
-            have = memcmp(cc, c.pre_x, (size_t)n * 8) == 0;
-            c.pre_x = nullptr;
-            c.rc = poll_values(c.sums_host, 1 + n, c.stream);
-            if (c.rc) return c.rc;
-        }
-#ifndef TTM_HOST_ONLY
-        if (!have && c.server && !c.box) {                   // the first evaluation of the loop: start its server
-            c.box = (unsigned char*)ttm_mailbox_acquire();
-            if (c.box) {
-                c.gen = ++g_server_gen;
-                c.round = 0;
-                const ServerArgs& a = *c.server;
-                const int rc = ttm_objective_sep_server_start(a.dPsi, a.ldp, a.N, a.m, a.delta, a.work, c.sums_host, c.box, c.gen, c.stream);
-                if (rc != TTM_OK) { ttm_mailbox_release(c.box); c.box = nullptr; }
-            }
-            if (!c.box) c.server = nullptr;                  // (no mailbox / a larger grid / switched off: a launch per evaluation)
-        }
-#endif
-        if (have) {
-        } else if (c.closed && c.have0 && cc[0] + c.delta > 0.0) {
-            c.sums_host[0] = c.Nw * log(cc[0] + c.delta) + c.KN;
-            c.sums_host[1] = c.Nw / (cc[0] + c.delta);
-#ifndef TTM_HOST_ONLY
-        } else if (c.box) {
-            // request: the coefficients, then - behind a store fence: the mailbox is a write-combining mapping - the word that
-            // announces them; the results arrive where a launch per evaluation puts them
-            // (tests: TTM_SRV_TEST_STALL = k makes the host miss the server's 0.2 s in front of request k of every loop)
-            static const int stall_at = [] { const char* e = getenv("TTM_SRV_TEST_STALL"); return e ? atoi(e) : 0; }();
-            if (stall_at > 0 && (int)c.round + 1 == stall_at) std::this_thread::sleep_for(std::chrono::milliseconds(300));
-            for (int attempt = 0;; ++attempt) {
-                arm_values(c.sums_host, 1 + n);
-                volatile double* bc = (volatile double*)(c.box + 8);
-                for (int i = 0; i < n; ++i) bc[i] = cc[i];
-                _mm_sfence();
-                *(volatile uint64_t*)c.box = ((uint64_t)c.gen << 32) | (uint64_t)(++c.round);
-                _mm_sfence();
-                bool unanswered = false;
-                c.rc = poll_values(c.sums_host, 1 + n, c.stream, &unanswered);
-                if (!c.rc || !unanswered || attempt >= 2) break;
-                // no answer and the stream idle: the server waited 0.2 s for this request (a host thread that was not scheduled) and
-                // left - both regions of the rows armed, as it leaves them between requests.  A new one takes over.
-                const ServerArgs& a = *c.server;
-                c.gen = ++g_server_gen;
-                c.round = 0;
-                if (ttm_objective_sep_server_start(a.dPsi, a.ldp, a.N, a.m, a.delta, a.work, c.sums_host, c.box, c.gen, c.stream) != TTM_OK) break;
-            }
-            if (c.rc) return c.rc;
-#endif
-        } else if (c.sent) {
-            arm_values(c.sums_host, 1 + n);
-            c.rc = c.sent(cc, c.sums_host, c.stream, c.sent_user);
-            if (c.rc) return c.rc;
-            c.rc = poll_values(c.sums_host, 1 + n, c.stream);
-            if (c.rc) return c.rc;
-        } else if (!c.comm) {                                // results and completion mark from the reduction itself
-            c.rc = objective_and_wait(c.sums_host + 1 + n, c.seq, c.stream,
-                                      [&](double* flag, double mark) { return c.launch(cc, out, flag, mark, c.stream); });
-            if (c.rc) return c.rc;
-        } else {
-            c.rc = c.launch(cc, out, (double*)nullptr, 0.0, c.stream);
-            if (c.rc) return c.rc;
-            c.rc = ttm_allreduce_f64(c.comm, c.sums_dev, 1 + n, TTM_OP_SUM, c.stream);
-            if (c.rc) return c.rc;
-#ifdef TTM_HOST_ONLY
-            memcpy(c.sums_host, c.sums_dev, (size_t)(1 + n) * 8);
-#else
-            if (hipMemcpyAsync(c.sums_host, c.sums_dev, (size_t)(1 + n) * 8, hipMemcpyDeviceToHost, (hipStream_t)c.stream) != hipSuccess)
-                return c.rc = TTM_E_HIP;
-#endif
-            c.rc = wait_for_mark(c.sums_host + 1 + n, c.seq, c.stream);
-            if (c.rc) return c.rc;
-        }
-        if (c.closed && !c.have0 && cc[0] + c.delta > 0.0) {  // the point the closed form is anchored at
-            const double nw = c.sums_host[1] * (cc[0] + c.delta), kn = c.sums_host[0] - nw * log(cc[0] + c.delta);
-            if (nw > 0.0 && nw < 1.0e300 && kn == kn && kn > -1.0e300 && kn < 1.0e300) { c.Nw = nw; c.KN = kn; c.have0 = true; }
-            else c.closed = false;                           // (a vanishing or negative derivative somewhere: the sums stay on the device)
-        }
-        // J = c'Ac/2 - sum log dS / N + c.b,  grad = Ac - sums/N + b   (TM:3008-3018)
-        double quad = 0.0, lin = 0.0;
-        for (int i = 0; i < n; ++i) {
-            double ax = 0.0;
-            for (int j = 0; j < n; ++j) ax += c.A[i * n + j] * cc[j];
-            quad += cc[i] * ax;
-            lin += cc[i] * c.b[i];
-            g[i] = ax - c.sums_host[1 + i] * c.invN + c.b[i];
-        }
-        *f = quad / 2.0 - c.sums_host[0] * c.invN + lin;
-        return 0;
-    };
-    const int rc = ttm_lbfgsb_minimize(m, x, lb, ub, fun, &c, maxiter, result);
-#ifndef TTM_HOST_ONLY
-    if (c.box) {                                             // the loop is over: the server leaves (and would by itself after 0.2 s)
-        *(volatile uint64_t*)c.box = ((uint64_t)c.gen << 32) | 0xffffffffull;
-        _mm_sfence();
-        ttm_mailbox_release(c.box);
-    }
-#endif
-    return c.rc ? c.rc : rc;
-}
-
-
-
 bool closed_form_enabled() {
     static const bool closed = [] { const char* e = getenv("TTM_SEP_CLOSED_FORM"); return !e || atoi(e) != 0; }();
     return closed;
 }
 
-// ttm_optimize_separable; pre_x != NULL: the rows of `work` are armed and an evaluation at pre_x is in flight (results: sums_host)
-int optimize_separable_cached(const double* dPsi, int64_t ldp, int64_t N, int32_t m, const double* A, const double* b, double Ntotal,
-                              double delta, const double* lb, const double* ub, double* x, double* work, uint32_t* counter,
-                              double* sums_dev, double* sums_host, ttm_comm* comm, void* stream, int32_t maxiter, double* result,
-                              const double* pre_x, int32_t* armed = nullptr) {
-    auto launch = [&](const double* cc, double* out, double* flag, double mark, void* st) {
-        return ttm_objective_sep_cached_marked(dPsi, ldp, N, m, cc, delta, work, counter, out, flag, mark, st);
-    };
-    // up to 128 workgroups and no communicator: evaluations with self-validating partial sums and results (ttm_sentinel_fill
-    // arms the rows once; every evaluation leaves them armed)
-    struct SentArgs { const double* dPsi; int64_t ldp, N; int32_t m; double delta; double* work; } sa{dPsi, ldp, N, m, delta, work};
-    SentLaunch sent = nullptr;
-    // (armed: the caller vouches that a previous loop on this `work` left the rows armed for the same m and N - no fill launch)
-    if (!comm && (pre_x || (armed && *armed) || ttm_sentinel_fill(work, m, N, stream) == TTM_OK))
-        sent = [](const double* cc, double* out_host, void* st, void* user) -> int {
-            const SentArgs& a = *(const SentArgs*)user;
-            return ttm_objective_sep_cached_sent(a.dPsi, a.ldp, a.N, a.m, cc, a.delta, a.work, out_host, st);
-        };
-    const ServerArgs srv{dPsi, ldp, N, m, delta, work};
-    const int rc = optimize_separable_with(launch, m, A, b, Ntotal, lb, ub, x, sums_dev, sums_host, comm, stream, maxiter, result,
-                                           closed_form_enabled() ? delta : -1.0, sent, &sa, pre_x, sent ? &srv : nullptr);
-    if (armed) *armed = (sent && rc == TTM_OK) ? 1 : 0;
-    return rc;
+// The checks every entry point of the separable loops makes before anything is launched or indexed.  A task evaluates from the
+// cached derivative basis (dPsi) or recomputes it from the x_k column (xk, kinds, pars).
+int check_task(const ttm_sep_task& q, int64_t N, double Ntotal, const double* sums_dev, const ttm_comm* comm) {
+    if ((q.dPsi ? q.ldp < N : (!q.xk || !q.kinds || !q.pars)) || !q.A || !q.b || !q.x || !q.work || !q.counter || !q.sums_host ||
+        q.m < 1 || N < 1 || !(Ntotal > 0.0) || (comm && !sums_dev))
+        return TTM_E_ARG;
+    return q.m > 16 ? TTM_E_LIMIT : TTM_OK;                 // (TTM_SEPC_MAXM of csrc/ttm_kernels.hip: the launches' limit)
 }
 
-// one task of ttm_optimize_separable_batch on stream st
-int run_task(ttm_sep_task& q, int64_t N, double Ntotal, double delta, void* st, int32_t maxiter) {
-    if (q.dPsi)
-        return q.rc = (!q.A || !q.b || !q.x || !q.work || !q.counter || !q.sums_host || q.m < 1 || !(Ntotal > 0.0))
-                          ? (int)TTM_E_ARG
-                          : optimize_separable_cached(q.dPsi, q.ldp, N, q.m, q.A, q.b, Ntotal, delta, q.lb, q.ub, q.x, q.work, q.counter, nullptr,
-                                                      q.sums_host, nullptr, st, maxiter, q.result, nullptr, &q.armed);
-    // derivative basis recomputed from the x_k column per evaluation
-    if (!q.xk || !q.kinds || !q.pars || !q.A || !q.b || !q.x || !q.work || !q.counter || !q.sums_host || q.m < 1 || !(Ntotal > 0.0))
-        return q.rc = TTM_E_ARG;
-    auto launch = [&](const double* cc, double* out, double* flag, double mark, void* s2) {
-        return ttm_objective_sep_direct_marked(q.xk, N, q.m, q.kinds, q.pars, cc, delta, q.work, q.counter, out, flag, mark, s2);
+std::atomic<uint32_t> g_server_gen{0};
+
+// The evaluation of one loop - sums_host[0] = sum_n log dS_n, sums_host[1 + i] = sum_n dPsi_{n,i} / dS_n (TM:2990-3006) at the
+// trial point cc, or an error code - in one of four ways, chosen before the loop starts (choose):
+//   SERVER  ONE launch answers every evaluation of the loop (k_objective_sep_server, cached basis, m > 1): requests through a
+//           mailbox the evaluator holds until it is destroyed;
+//   SENT    a launch per evaluation with self-validating partial sums and results (no ticket, no mark);
+//   MARKED  a launch per evaluation that writes its results and a completion mark;
+//   COMM    a launch into sums_dev, the all-reduce over the ranks, the copy to sums_host and a completion mark behind them.
+// A server that leaves unasked (its 0.2 s without a request ran out) or gives up (the FAIL pattern) is replaced - at most three
+// servers per loop - and then the loop goes on with SENT: the same bits every way.
+struct Evaluator {
+    enum Kind { MARKED, SENT, SERVER, COMM };
+    const ttm_sep_task& q;
+    int64_t N;
+    double delta;
+    double* sums_dev;
+    ttm_comm* comm;
+    void* stream;
+    Kind kind = MARKED;
+    long seq = 0;                                            // MARKED / COMM: the last completion mark
+    unsigned char* box = nullptr;                            // SERVER: the mailbox (fine-grained device memory, host-written)
+    uint32_t gen = 0, round = 0;                             //   the running server's generation and its last request
+    int starts = 0;                                          //   servers started in this loop
+
+    Evaluator(const ttm_sep_task& q_, int64_t N_, double delta_, double* sums_dev_, ttm_comm* comm_, void* stream_)
+        : q(q_), N(N_), delta(delta_), sums_dev(sums_dev_), comm(comm_), stream(stream_) {}
+    Evaluator(const Evaluator&) = delete;                    // (it owns the mailbox)
+    ~Evaluator() { drop_server(); }                          // (the server leaves; it would by itself after 0.2 s)
+
+    // armed_ahead: an evaluation with self-validating sums is in flight already (the rows of `work` are armed).  Returns the layout
+    // key of the rows this loop leaves armed (ttm_sep_task.armed), 0 for MARKED / COMM.
+    int choose(bool armed_ahead) {
+        const int key = comm ? 0 : sentinel_layout(q.m, N);
+        if (!key || !(armed_ahead || q.armed == key || ttm_sentinel_fill(q.work, q.m, N, stream) == TTM_OK)) {
+            kind = comm ? COMM : MARKED;
+            q.sums_host[1 + q.m] = 0.0;                      // the completion mark (sums_host: >= 2 + m doubles)
+            return 0;
+        }
+        kind = SENT;
+        if (q.dPsi && q.m > 1 && (box = (unsigned char*)ttm_mailbox_acquire()) != nullptr) {
+            if (start_server()) kind = SERVER;
+            else drop_server();
+        }
+        return key;
+    }
+
+    int eval(const double* cc) {
+        switch (kind) {
+        case SERVER: return serve(cc);
+        case SENT: {
+            arm_values(q.sums_host, 1 + q.m);
+            const int rc = q.dPsi ? ttm_objective_sep_cached_sent(q.dPsi, q.ldp, N, q.m, cc, delta, q.work, q.sums_host, stream)
+                                  : ttm_objective_sep_direct_sent(q.xk, N, q.m, q.kinds, q.pars, cc, delta, q.work, q.sums_host, stream);
+            return rc ? rc : poll_values(q.sums_host, 1 + q.m, stream);
+        }
+        case MARKED:
+            return objective_and_wait(q.sums_host + 1 + q.m, seq, stream,
+                                      [&](double* flag, double mark) { return launch_marked(cc, q.sums_host, flag, mark); });
+        case COMM: {
+            int rc = launch_marked(cc, sums_dev, nullptr, 0.0);
+            if (!rc) rc = ttm_allreduce_f64(comm, sums_dev, 1 + q.m, TTM_OP_SUM, stream);
+            if (!rc) rc = copy_to_host(q.sums_host, sums_dev, 1 + q.m, stream);
+            return rc ? rc : wait_for_mark(q.sums_host + 1 + q.m, seq, stream);
+        }
+        }
+        return TTM_E_ARG;
+    }
+
+  private:
+    int launch_marked(const double* cc, double* out, double* flag, double mark) {
+        return q.dPsi ? ttm_objective_sep_cached_marked(q.dPsi, q.ldp, N, q.m, cc, delta, q.work, q.counter, out, flag, mark, stream)
+                      : ttm_objective_sep_direct_marked(q.xk, N, q.m, q.kinds, q.pars, cc, delta, q.work, q.counter, out, flag, mark, stream);
+    }
+
+    bool start_server() {
+        gen = ++g_server_gen;
+        round = 0;
+        ++starts;
+        return ttm_objective_sep_server_start(q.dPsi, q.ldp, N, q.m, delta, q.work, q.sums_host, box, gen, stream) == TTM_OK;
+    }
+
+    void post(uint32_t word) {                               // (the mailbox is a write-combining mapping: fenced stores)
+        *(volatile uint64_t*)box = ((uint64_t)gen << 32) | word;
+        store_fence();
+    }
+
+    void drop_server() {
+        if (!box) return;
+        post(0xffffffffu);
+        ttm_mailbox_release(box);
+        box = nullptr;
+    }
+
+    // request: the coefficients, then - behind a store fence - the word that announces them; the results arrive where a launch
+    // per evaluation puts them (tests: TTM_SRV_TEST_STALL = k makes the host miss the server's 0.2 s in front of request k)
+    int serve(const double* cc) {
+        static const int stall_at = [] { const char* e = getenv("TTM_SRV_TEST_STALL"); return e ? atoi(e) : 0; }();
+        if (stall_at > 0 && (int)round + 1 == stall_at) std::this_thread::sleep_for(std::chrono::milliseconds(300));
+        for (;;) {
+            arm_values(q.sums_host, 1 + q.m);
+            volatile double* bc = (volatile double*)(box + 8);
+            for (int i = 0; i < q.m; ++i) bc[i] = cc[i];
+            store_fence();
+            post(++round);
+            bool retry = false;
+            int rc = poll_values(q.sums_host, 1 + q.m, stream, &retry);
+            if (!rc || !retry) return rc;
+            // no answer with the stream idle, or the FAIL pattern: the server has left or gives up.  Make sure every workgroup has
+            // left, then re-arm both regions of the rows (a workgroup that stored late may have dirtied one) before anything else
+            // evaluates on them.
+            post(0xffffffffu);
+            if ((rc = stream_idle(stream)) != TTM_OK || (rc = ttm_sentinel_fill(q.work, q.m, N, stream)) != TTM_OK) return rc;
+            if (starts < 3 && start_server()) continue;
+            drop_server();
+            kind = SENT;
+            return eval(cc);
+        }
+    }
+};
+
+// The L-BFGS-B loop of one component (TM:2978-3018, TM:3108-3114) behind the checks of every entry point.  pre_x != NULL: the
+// rows of q.work are armed and an evaluation at pre_x with self-validating results is in flight on `stream` (results: sums_host);
+// the loop's first evaluation uses it when it is at that point, and it is waited for whatever happens.  q.armed, in: the layout
+// key (sentinel_layout) the rows of q.work were left armed with; out: the key this loop leaves them armed with, or 0.
+//
+// ONE monotone term (m = 1: the filtering and smoothing maps of Examples C, most components of Markov-type maps): the sample
+// sums are known in closed form once they have been taken at one point.  dS_n = dPsi_n c + delta dPsi_n = dPsi_n (c + delta)
+// (TM:2990-2993), so sum_n log dS_n = N log(c + delta) + sum_n log dPsi_n and sum_n dPsi_n / dS_n = N / (c + delta): the
+// first evaluation of the loop goes to the device, every later one is two host operations - the same function to
+// rounding (1e-16 relative, like the order of a reduction), no launch, no round trip.
+int run_task(ttm_sep_task& q, int64_t N, double Ntotal, double delta, double* sums_dev, ttm_comm* comm, void* stream, int32_t maxiter,
+             double* result, const double* pre_x) {
+    if (const int arg_rc = check_task(q, N, Ntotal, sums_dev, comm)) return q.rc = arg_rc;
+    struct Loop {
+        Evaluator ev;
+        const ttm_sep_task& q;
+        double invN, delta;
+        const double* pre_x;                                 // the evaluation launched ahead, until it has been waited for
+        bool closed, have0;
+        double Nw, KN;                                       // closed form of m = 1: weights N, sum_n log dPsi_n
+        int rc;
+    } L{{q, N, delta, sums_dev, comm, stream}, q, 1.0 / Ntotal, delta, pre_x,
+        q.dPsi && closed_form_enabled() && q.m == 1 && delta >= 0.0 && q.lb && q.lb[0] >= 0.0, false, 0.0, 0.0, 0};
+    const int key = L.ev.choose(pre_x != nullptr);
+    auto fun = [](int32_t n, const double* cc, double* f, double* g, void* user) -> int32_t {
+        Loop& L = *(Loop*)user;
+        double* sums = L.q.sums_host;
+        if (L.pre_x) {                                       // the evaluation that was launched ahead: wait for it whatever it is good for
+            const bool have = memcmp(cc, L.pre_x, (size_t)n * 8) == 0;
+            L.pre_x = nullptr;
+            if ((L.rc = poll_values(sums, 1 + n, L.ev.stream)) || (!have && (L.rc = L.ev.eval(cc)))) return L.rc;
+        } else if (L.closed && L.have0 && cc[0] + L.delta > 0.0) {
+            sums[0] = L.Nw * log(cc[0] + L.delta) + L.KN;
+            sums[1] = L.Nw / (cc[0] + L.delta);
+        } else if ((L.rc = L.ev.eval(cc))) return L.rc;
+        if (L.closed && !L.have0 && cc[0] + L.delta > 0.0) {  // the point the closed form is anchored at
+            const double nw = sums[1] * (cc[0] + L.delta), kn = sums[0] - nw * log(cc[0] + L.delta);
+            if (nw > 0.0 && nw < 1.0e300 && kn == kn && kn > -1.0e300 && kn < 1.0e300) { L.Nw = nw; L.KN = kn; L.have0 = true; }
+            else L.closed = false;                           // (a vanishing or negative derivative somewhere: the sums stay on the device)
+        }
+        // J = c'Ac/2 - sum log dS / N + c.b,  grad = Ac - sums/N + b   (TM:3008-3018)
+        double quad = 0.0, lin = 0.0;
+        for (int i = 0; i < n; ++i) {
+            double ax = 0.0;
+            for (int j = 0; j < n; ++j) ax += L.q.A[i * n + j] * cc[j];
+            quad += cc[i] * ax;
+            lin += cc[i] * L.q.b[i];
+            g[i] = ax - sums[1 + i] * L.invN + L.q.b[i];
+        }
+        *f = quad / 2.0 - sums[0] * L.invN + lin;
+        return 0;
     };
-    // (self-validating sums as in ttm_optimize_separable: the same finish, hence the same bits, as the cached basis)
-    struct SentArgs { const ttm_sep_task* q; int64_t N; double delta; } sa{&q, N, delta};
-    SentLaunch sent = nullptr;
-    if (q.armed || ttm_sentinel_fill(q.work, q.m, N, st) == TTM_OK)
-        sent = [](const double* cc, double* out_host, void* s2, void* user) -> int {
-            const SentArgs& a = *(const SentArgs*)user;
-            return ttm_objective_sep_direct_sent(a.q->xk, a.N, a.q->m, a.q->kinds, a.q->pars, cc, a.delta, a.q->work, out_host, s2);
-        };
-    q.rc = optimize_separable_with(launch, q.m, q.A, q.b, Ntotal, q.lb, q.ub, q.x, nullptr, q.sums_host, nullptr, st, maxiter,
-                                   q.result, -1.0, sent, &sa);
-    q.armed = (sent && q.rc == TTM_OK) ? 1 : 0;
+    const int rc = ttm_lbfgsb_minimize(q.m, q.x, q.lb, q.ub, fun, &L, maxiter, result);
+    // (a loop that ended before its first evaluation: `work` and sums_host go back to the caller once nothing writes them)
+    const int ahead_rc = L.pre_x ? poll_values(q.sums_host, 1 + q.m, stream) : TTM_OK;
+    q.rc = L.rc ? L.rc : ahead_rc ? ahead_rc : rc;
+    q.armed = q.rc == TTM_OK ? key : 0;
     return q.rc;
 }
 
@@ -434,65 +447,51 @@ extern "C" {
 int ttm_optimize_separable(const double* dPsi, int64_t ldp, int64_t N, int32_t m, const double* A, const double* b, double Ntotal,
                            double delta, const double* lb, const double* ub, double* x, double* work, uint32_t* counter,
                            double* sums_dev, double* sums_host, ttm_comm* comm, void* stream, int32_t maxiter, double* result) {
-    if (!dPsi || !A || !b || !x || !work || !counter || !sums_host || m < 1 || N < 1 || !(Ntotal > 0.0)) return TTM_E_ARG;
-    if (comm && !sums_dev) return TTM_E_ARG;
-    return optimize_separable_cached(dPsi, ldp, N, m, A, b, Ntotal, delta, lb, ub, x, work, counter, sums_dev, sums_host, comm, stream, maxiter,
-                                     result, nullptr);
+    if (!dPsi) return TTM_E_ARG;                             // (the cached basis only: a task without it reads the x_k column)
+    ttm_sep_task q{};
+    q.dPsi = dPsi; q.ldp = ldp; q.m = m; q.A = A; q.b = b; q.lb = lb; q.ub = ub; q.x = x;
+    q.work = work; q.counter = counter; q.sums_host = sums_host;
+    return run_task(q, N, Ntotal, delta, sums_dev, comm, stream, maxiter, result, nullptr);
 }
 
 int ttm_optimize_separable_batch(ttm_sep_task* tasks, int32_t ntasks, int64_t N, double Ntotal, double delta, int32_t nthreads,
                                  void* stream, int32_t maxiter) {
     if (!tasks || ntasks < 1 || N < 1) return TTM_E_ARG;
-#ifndef TTM_HOST_ONLY
-    // Components with ONE monotone term need one device evaluation (the closed form of optimize_separable_with takes over behind it).
-    // When at most one other component is in the batch - the filter's maps: two such components and one with special terms - no
-    // threads: the first evaluations of the one-term components are launched ahead on `stream`, the other component's loop runs
-    // behind them, and the one-term loops find their sums in place (a thread per component cost ~40 us each to start and fought
-    // the long loop for the runtime's launch lock).  The same evaluations at the same points: the same bits as the threaded batch.
-    {
-        std::vector<int> ahead, rest;
-        for (int t = 0; t < ntasks; ++t) {
-            const ttm_sep_task& q = tasks[t];
-            const bool one = q.dPsi && q.m == 1 && closed_form_enabled() && delta >= 0.0 && q.lb && q.lb[0] >= 0.0 && q.A && q.b && q.x &&
-                             q.work && q.counter && q.sums_host;
-            (one ? ahead : rest).push_back(t);
-        }
-        if (!ahead.empty() && rest.size() <= 1 && Ntotal > 0.0) {
-            std::vector<double> x0(ntasks, 0.0);
-            std::vector<char> flying(ntasks, 0);
-            int first_rc = TTM_OK;
-            for (int t : ahead) {
-                ttm_sep_task& q = tasks[t];
-                double v = q.x[0];                                       // the start as lbfgsb_minimize projects it
-                if (v <= q.lb[0]) v = q.lb[0];
-                else if (q.ub && q.ub[0] < INFINITY && v >= q.ub[0]) v = q.ub[0];
-                x0[t] = v;
-                if (!q.armed && ttm_sentinel_fill(q.work, 1, N, stream) != TTM_OK) continue;
-                arm_values(q.sums_host, 2);
-                if (ttm_objective_sep_cached_sent(q.dPsi, q.ldp, N, 1, &x0[t], delta, q.work, q.sums_host, stream) == TTM_OK) flying[t] = 1;
-            }
-            auto run_one = [&](int t) {
-                ttm_sep_task& q = tasks[t];
-                if (!q.dPsi) return -1;
-                q.rc = optimize_separable_cached(q.dPsi, q.ldp, N, q.m, q.A, q.b, Ntotal, delta, q.lb, q.ub, q.x, q.work, q.counter, nullptr,
-                                                 q.sums_host, nullptr, stream, maxiter, q.result, flying[t] ? &x0[t] : nullptr, &q.armed);
-                if (q.rc && !first_rc) first_rc = q.rc;
-                return 0;
-            };
-            bool direct_rest = false;
-            for (int t : rest) if (run_one(t) < 0) direct_rest = true;
-            for (int t : ahead) run_one(t);
-            if (!direct_rest) return first_rc;
-            // (the other component recomputes its basis: it takes the general path below, alone)
-            if (first_rc) return first_rc;
-            const int t = rest[0];
-            return run_batch(1, 1, stream, [&](int, void* st) { return run_task(tasks[t], N, Ntotal, delta, st, maxiter); });
-        }
+    // Components with ONE monotone term need one device evaluation (the closed form of run_task takes over behind it).  When at
+    // most one other component is in the batch - the filter's maps: two such components and one with special terms - no threads:
+    // the first evaluations of the one-term components are launched ahead on `stream`, the other component's loop runs behind
+    // them, and the one-term loops find their sums in place (a thread per component cost ~40 us each to start and fought the long
+    // loop for the runtime's launch lock).  The same evaluations at the same points: the same bits as the threaded batch.
+    std::vector<int> ahead, rest;
+    for (int t = 0; t < ntasks; ++t) {
+        const ttm_sep_task& q = tasks[t];
+        const bool one = q.dPsi && q.m == 1 && closed_form_enabled() && delta >= 0.0 && check_task(q, N, Ntotal, nullptr, nullptr) == TTM_OK &&
+                         q.lb && q.lb[0] >= 0.0;
+        (one ? ahead : rest).push_back(t);
     }
-#endif
-    return run_batch(ntasks, nthreads, stream, [&](int t, void* st) { return run_task(tasks[t], N, Ntotal, delta, st, maxiter); });
+    if (ahead.empty() || rest.size() > 1)
+        return run_batch(ntasks, nthreads, stream, [&](int t, void* st) {
+            return run_task(tasks[t], N, Ntotal, delta, nullptr, nullptr, st, maxiter, tasks[t].result, nullptr);
+        });
+    std::vector<double> x0(ntasks, 0.0);
+    std::vector<char> flying(ntasks, 0);
+    const int key = sentinel_layout(1, N);
+    for (int t : ahead) {
+        ttm_sep_task& q = tasks[t];
+        double v = q.x[0];                                   // the start as lbfgsb_minimize projects it
+        if (v <= q.lb[0]) v = q.lb[0];
+        else if (q.ub && q.ub[0] < INFINITY && v >= q.ub[0]) v = q.ub[0];
+        x0[t] = v;
+        if (!key || (q.armed != key && ttm_sentinel_fill(q.work, 1, N, stream) != TTM_OK)) continue;
+        arm_values(q.sums_host, 2);
+        flying[t] = ttm_objective_sep_cached_sent(q.dPsi, q.ldp, N, 1, &x0[t], delta, q.work, q.sums_host, stream) == TTM_OK;
+    }
+    for (int t : rest) run_task(tasks[t], N, Ntotal, delta, nullptr, nullptr, stream, maxiter, tasks[t].result, nullptr);
+    for (int t : ahead) run_task(tasks[t], N, Ntotal, delta, nullptr, nullptr, stream, maxiter, tasks[t].result, flying[t] ? &x0[t] : nullptr);
+    for (int t = 0; t < ntasks; ++t)
+        if (tasks[t].rc) return tasks[t].rc;
+    return TTM_OK;
 }
-
 
 // (Gnn + ridge I)^-1 Gnm by Cholesky on the diagonally equilibrated matrix with one step of iterative refinement - the host
 // class's _normal_solve, ridge > 0.  G: the (n + m) x (n + m) Gram matrix, row-major; y: n x m.  false: not positive
