@@ -44,24 +44,7 @@ __host__ __device__ constexpr int rec_stride(int cls, int lag) { return (TTM_P_H
 #define BAND_ET_DOUBLES (2 * TTM_BAND_ET_N)          /* 12 816 bytes: a multiple of 16 */
 #define BAND_CT 1024                                 /* threads per workgroup */
 #define BAND_NS 4                                    /* rows per thread: pairs (2t, 2t+1) of the two halves of a tile */
-#ifndef BAND_ROWS_TOGETHER
-#define BAND_ROWS_TOGETHER 2                         /* rows of a thread whose instructions the scheduler may interleave (1, 2, 4) */
-#endif
-#ifndef BAND_FWD_NT
-#define BAND_FWD_NT 0                                /* non-temporal stores of the forward map's columns */
-#endif
-#ifndef BAND_INV_NT
-#define BAND_INV_NT 0
-#endif
-#ifndef BAND_FWD_NTL
-#define BAND_FWD_NTL 0                               /* non-temporal loads of the forward map's columns */
-#endif
-#ifndef BAND_INV_NTL
-#define BAND_INV_NTL 0
-#endif
-#ifndef BAND_PF
 #define BAND_PF 1                                    /* columns requested ahead of the one being evaluated */
-#endif
 
 // One LDS-DMA instruction (16 bytes per lane: the wave's 1 KB lands at lds_wave_base, an LDS byte address, lane after lane),
 // written in assembly so that the COMPILER DOES NOT KNOW IT: with a global_load_lds it knows to be in flight hipcc waits for
@@ -155,8 +138,8 @@ __global__ __launch_bounds__(64) void k_band_records(const int* __restrict__ uco
     }
 }
 
-// column stream accesses: 16 bytes per lane.  The forward map's stores are non-temporal (written once, 320 MB: -6 % launch
-// time against plain stores, profiles/r03_*; for the loads and for the inverse's stores the hint changes nothing)
+// column stream accesses: 16 bytes per lane.  The forward map and the inverse load and store plainly: what one launch leaves
+// in the Infinity Cache is what the next one reads.  The few-component kernels' column stores are non-temporal.
 template <bool NT>
 __device__ __forceinline__ void band_store2(char* p, double a, double b) {
     typedef double v2 __attribute__((ext_vector_type(2)));
@@ -164,12 +147,9 @@ __device__ __forceinline__ void band_store2(char* p, double a, double b) {
     if (NT) __builtin_nontemporal_store(v, (v2*)p);
     else *(v2*)p = v;
 }
-template <bool NT = false>
 __device__ __forceinline__ D2 band_load2(const char* p) {
     typedef double v2 __attribute__((ext_vector_type(2)));
-    v2 v;
-    if (NT) v = __builtin_nontemporal_load((const v2*)p);
-    else v = *(const v2*)p;
+    const v2 v = *(const v2*)p;
     const D2 r = {v.x, v.y};
     return r;
 }
@@ -281,14 +261,14 @@ __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const dou
     for (int i = 0; i < PF; ++i) {
         const char* xc0 = xcol + (int64_t)(kb + i < ke ? i : 0) * ldxb;
 #pragma unroll
-        for (int q = 0; q < NP; ++q) xr[i][q] = band_load2<BAND_FWD_NTL != 0>(xc0 + roff[q]);
+        for (int q = 0; q < NP; ++q) xr[i][q] = band_load2(xc0 + roff[q]);
     }
     cdbl_p rec = P + (int64_t)(kb + LAG) * PS;
     auto step = [&](int j, const D2 (&xc)[NP], D2 (&xn)[NP]) {
         {
             const char* xnext = j + PF < ke ? xcol + PF * ldxb : xcol;        // (past the block: a harmless re-read)
 #pragma unroll
-            for (int q = 0; q < NP; ++q) xn[q] = band_load2<BAND_FWD_NTL != 0>(xnext + roff[q]);
+            for (int q = 0; q < NP; ++q) xn[q] = band_load2(xnext + roff[q]);
         }
         __builtin_amdgcn_sched_barrier(0);                    // (the scheduler would sink the loads to the end of the step)
         // ---- uniform data of the step ------------------------------------------------------------------------
@@ -296,8 +276,8 @@ __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const dou
         cint_p ri = (cint_p)rec;
         const int nI = ri[10];
         const double* tab = tabs + (ri[11] - tab0);
-        // ---- row by row (BAND_ROWS_TOGETHER of them scheduled together: each needs 24 registers for its coefficients; the
-        // waves of the SIMD, not the rows of a thread, fill each other's latencies) ------------------------------------
+        // ---- row by row (two of them scheduled together: each needs 24 registers for its coefficients; the waves of the
+        // SIMD, not the rows of a thread, fill each other's latencies) -------------------------------------------------
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
             double zv[2];
@@ -305,34 +285,17 @@ __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const dou
             for (int h = 0; h < 2; ++h) {
                 const int e = 2 * q + h;
                 const double x = h ? xc[q].y : xc[q].x;
-#ifdef BAND_X_NOSPLINE                                       /* (timing experiments: results wrong by construction) */
-                const double m = x;
-#else
                 const double m = band_spline(tab, nI, sp_a, sp_b, sp_ds, x);
-#endif
-#ifdef BAND_X_NOEXP
-                const double E = x;
-#else
                 const double E = band_expq(etab, x, kt);
-#endif
                 zv[h] = pend[e][0] + m;
-#ifdef BAND_X_NOPUSH
-                pend[e][0] = E;
-#else
                 band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, x, E, pend[e]);
-#endif
-                if (BAND_ROWS_TOGETHER == 1) __builtin_amdgcn_sched_barrier(0);
             }
             const unsigned int n = tbase + (unsigned int)(q * HALF);
             const D2 o = {zv[0], zv[1]};
             char* zp = zcol + (size_t)(n * 8u);
-#ifdef BAND_X_NOSTORE
-            if (o.x == 1.2345e300) *(D2*)zp = o;
-#else
-            if (FULL || n + 1 < c1_32) band_store2<BAND_FWD_NT != 0>(zp, o.x, o.y);
+            if (FULL || n + 1 < c1_32) band_store2<false>(zp, o.x, o.y);
             else if (n < c1_32) *(double*)zp = o.x;
-#endif
-            if (BAND_ROWS_TOGETHER <= 2) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         rec += PS; xcol += ldxb; zcol += ldzb;
     };
@@ -404,12 +367,7 @@ __device__ __forceinline__ void band_spline_d(const double* tab, int nI, double 
 // spline, 1/sigma_k) enter as one number per launch.
 #define BAND_LD_CHUNK 2
 #define BAND_UNI 256                                  /* components of a density pass, at most */
-#ifndef BAND_DENS_RT
-#define BAND_DENS_RT 2
-#endif
-#ifndef BAND_DENS_NS
 #define BAND_DENS_NS 4
-#endif
 template <int CLS, int LAG, bool WRITE_Z>
 __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                           const double* __restrict__ X, int64_t ldx, int64_t N,
@@ -539,9 +497,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restri
                         prod[e] *= dm;
                         dmin[e] = fmin(dmin[e], dm);
                         band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, x, E, pend[e]);
-                        if (BAND_DENS_RT == 1) __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (BAND_DENS_RT == 2) __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_sched_barrier(0);
                     if (WRITE_Z) {
                         const unsigned int n = tbase + (unsigned int)(q * HALF);
                         char* zp = zcol + (size_t)(n * 8u);
@@ -641,9 +598,7 @@ __device__ __forceinline__ double band_spline_dd(const double* tab, int nI, doub
     return fma(da, s, a);
 }
 
-#ifndef BAND_LD_PF
 #define BAND_LD_PF 3
-#endif
 template <int LAG, int NS>
 __global__ __launch_bounds__(BAND_CT) void k_band_logdet(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0, int ps,
                                                          const double* __restrict__ X, int64_t ldx, int64_t N,
@@ -731,14 +686,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_logdet(const double* __restric
             auto step = [&](int j, const D2 (&xc)[NP], D2 (&xn)[NP]) {
                 {
                     const char* xnext = j + PF < ke ? xcol + PF * ldxb : xcol;       // (past the block: a harmless re-read)
-#if defined(BAND_XL) && BAND_XL == 2                          /* (timing experiment: no column stream) */
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) { xn[q].x = xc[q].x + 1e-9; xn[q].y = xc[q].y - 1e-9; }
-                    (void)xnext;
-#else
 #pragma unroll
                     for (int q = 0; q < NP; ++q) xn[q] = band_load2(xnext + roff[q]);
-#endif
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const double sp_a = rec[2], sp_b = rec[3], sp_ds = rec[4], own1 = rec[7];
@@ -751,11 +700,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_logdet(const double* __restric
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
                             const int e = 2 * q + h;
-#if defined(BAND_XL) && BAND_XL == 1                          /* (timing experiment: results wrong by construction) */
-                            const double dm = h ? xc[q].y : xc[q].x;
-#else
                             const double dm = band_spline_dd(tab, nI, sp_a, sp_b, sp_ds, h ? xc[q].y : xc[q].x);
-#endif
                             prod[e] *= dm;
                             dmin[e] = fmin(dmin[e], dm);
                         }
@@ -906,18 +851,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_forward(const double* __restri
 // columns are walked in registers.  Same arithmetic per row as k_band_forward / k_band_density.
 // DENS: also sum_k log(dS_k/dx_k / sigma_k) and sum_k S_k^2 per row (Z optional)
 // ---------------------------------------------------------------------------
-#ifndef BAND_FEW_STAGE
-#define BAND_FEW_STAGE 0
-#endif
-#ifndef BAND_FEWI_STAGE
-#define BAND_FEWI_STAGE 0
-#endif
-#ifndef BAND_FEW_NS
 #define BAND_FEW_NS 2                                 /* rows per thread and tile of the few-component kernels */
-#endif
-#ifndef BAND_FEW_NT
-#define BAND_FEW_NT 1                                 /* non-temporal stores of the few-component kernels */
-#endif
 #define BAND_FEW_TAB (4 * BAND_CT)                    /* doubles of splines a launch can stage (two 16-byte loads per thread) */
 // LAG: groups per push record (u_p_lag); LAGE <= LAG: how far back a group of the sweep reaches; PLAIN: some group has
 // plain polynomial terms
@@ -936,9 +870,6 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few(const double* __restrict__
     double* tabs = g_lds + BAND_ET_DOUBLES;
     const int tid = threadIdx.x;
     const int nc = k1 - k0;
-#if BAND_FEW_STAGE == 1                                      /* (timing experiments: results wrong by construction) */
-    if (N > 0) return;
-#endif
     cdbl_p P = (cdbl_p)(U_ + p_off);
     cdbl_p kt = (cdbl_p)g_band_taylor;
     const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
@@ -1004,26 +935,6 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few(const double* __restrict__
         const bool more = tile + (int)gridDim.x < ntiles;
         if (more && !DENS) request(tile + gridDim.x, xfn, xinn);
         __builtin_amdgcn_sched_barrier(0);
-#if BAND_FEW_STAGE == 2 || BAND_FEW_STAGE == 3
-        {
-            double acc = etab[tid & 511] + tabs[tid & 255];
-#pragma unroll
-            for (int j = 0; j < FD; ++j)
-#pragma unroll
-                for (int q = 0; q < NP; ++q) acc += xin[j][q].x + xin[j][q].y;
-            if (BAND_FEW_STAGE == 3) {
-#pragma unroll
-                for (int j = 0; j < FD; ++j)
-                    if (j < nc)
-#pragma unroll
-                        for (int q = 0; q < NP; ++q) {
-                            const unsigned int n = tbase + (unsigned int)(q * HALF);
-                            if (n + 1 < N32) band_store2<false>((char*)Z + (int64_t)j * ldzb + (size_t)(n * 8u), acc, xin[j][q].y);
-                        }
-            } else if (acc == 1.2345e300) Z[tid] = acc;
-            continue;
-        }
-#endif
         double pend[NS][LAGE];
 #pragma unroll
         for (int l = 0; l < LAGE; ++l) {
@@ -1092,7 +1003,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few(const double* __restrict__
                     if (!DENS || Z) {
                         const unsigned int n = tbase + (unsigned int)(q * HALF);
                         char* zp = zcol + (size_t)(n * 8u);
-                        if (n + 1 < N32) band_store2<BAND_FEW_NT != 0>(zp, zv[0], zv[1]);
+                        if (n + 1 < N32) band_store2<true>(zp, zv[0], zv[1]);
                         else if (n < N32) *(double*)zp = zv[0];
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -1243,7 +1154,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
         for (int q = 0; q < NP; ++q) za[q] = zfirst[q];
     } else {
 #pragma unroll
-        for (int q = 0; q < NP; ++q) za[q] = band_load2<BAND_INV_NTL != 0>(zcol + roff[q]);
+        for (int q = 0; q < NP; ++q) za[q] = band_load2(zcol + roff[q]);
     }
     // interp1d slope form (TM:4062-4065) in the located interval and exp(-x^2/4) = E[i-1] exp(w), w = -delta (y_lo + x) / 4
     auto interp = [&](double y_lo, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
@@ -1266,7 +1177,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
         {
             const char* znext = j + 1 < ke ? zcol + cx.ldzb : zcol;           // (past the block: a harmless re-read)
 #pragma unroll
-            for (int q = 0; q < NP; ++q) zn[q] = band_load2<BAND_INV_NTL != 0>(znext + roff[q]);
+            for (int q = 0; q < NP; ++q) zn[q] = band_load2(znext + roff[q]);
         }
         // the record of the step, requested NOW (left to itself the compiler loads the group coefficients where the pushes
         // use them - at the end of the step's dependent chain, a scalar-cache round trip on the critical path)
@@ -1334,17 +1245,8 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
 #pragma unroll
             for (int e = 0; e < NS; ++e) interp(ey[e].y, xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
         };
-#if defined(BAND_XI_NOSEARCH)                                /* (timing experiments: results wrong by construction) */
-#pragma unroll
-        for (int e = 0; e < NS; ++e) interp(tg[e], wl, wh, scale, tg[e], r[e], E[e]);
-#elif defined(BAND_XI_NOSOLVE)
-#pragma unroll
-        for (int e = 0; e < NS; ++e) { r[e] = tg[e]; E[e] = traw[e]; }
-#else
         if (per <= 2) search(std::integral_constant<int, 2>());
         else search(std::integral_constant<int, 4>());
-#endif
-#ifndef BAND_XI_NOOUTL
         if (outl != 0) {
             // outliers (the tails of the table, beyond the window, NaN; every row of a degenerate table): clip as
             // TM:4074-4076, np.searchsorted (left) over the whole row in memory, the same interpolation
@@ -1366,22 +1268,13 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
                 }
             }
         }
-#endif
         // x_k is pushed on to the components that read it, and stored
-#ifdef BAND_XI_NOPUSH
-#pragma unroll
-        for (int e = 0; e < NS; ++e) pend[e][0] = E[e] * start;
-#else
 #pragma unroll
         for (int e = 0; e < NS; ++e) band_push<DB, DA, LAG>(gc, start, r[e], E[e], pend[e]);
-#endif
-#ifdef BAND_XI_NOSTORE
-        if (r[0] == 1.2345e300)
-#endif
         if (full) {
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
-                band_store2<BAND_INV_NT != 0>(xcol + (size_t)((tbase + (unsigned int)(q * HALF)) * 8u), r[2 * q], r[2 * q + 1]);
+                band_store2<false>(xcol + (size_t)((tbase + (unsigned int)(q * HALF)) * 8u), r[2 * q], r[2 * q + 1]);
             }
         } else {
 #pragma unroll
@@ -1404,9 +1297,6 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
                 __syncthreads();
             }
         }
-#ifdef BAND_XI_BARRIERS                                      /* (timing experiment: what a workgroup barrier every so many columns costs) */
-        if ((j - kb) % BAND_XI_BARRIERS == BAND_XI_BARRIERS - 1) __syncthreads();
-#endif
     };
     int j = kb;
     for (; j + 1 < ke; j += 2) {
@@ -1474,15 +1364,12 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse(const double* __restri
             for (int q = 0; q < NP; ++q) {
                 unsigned int n = (unsigned int)c0 + 2u * (unsigned int)tid + (unsigned int)(q * HALF);
                 n = n < last_pair ? n : last_pair;
-                zfirst[q] = band_load2<BAND_INV_NTL != 0>(zc0 + (size_t)(n * 8u));
+                zfirst[q] = band_load2(zc0 + (size_t)(n * 8u));
             }
         }
         __syncthreads();                                      // every wave is done with the previous block's tables
         // the tables of the block: every load of the block in flight at once (element i of every table by thread i; the
         // bucket indices sixteen bytes at a time), the search parameters next to them
-#ifdef BAND_XI_NOSWITCH                                      /* (timing experiment: later blocks search the first block's tables) */
-        if (kb == k0)
-#endif
         {
             constexpr int KMAX = KM;                          // components per block, at most (the host plans for it)
             double lo = 0.0, hi = 0.0;
@@ -1526,9 +1413,6 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse(const double* __restri
         }
         __syncthreads();
         // entries per bucket, at most; the value range [wl, wh] whose search stays inside the window (k_inverse_rt)
-#ifdef BAND_XI_NOSWITCH
-        if (kb == k0)
-#endif
         for (int c = tid >> 6; c < nk; c += CT >> 6) {
             const unsigned short* bs = (const unsigned short*)(tabs + (size_t)c * tab_slot + BAND_RT_HDR + Weven);
             int per = 0;
@@ -1649,7 +1533,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
     for (int q = 0; q < NP; ++q) {
         unsigned int n = (unsigned int)c0 + 2u * (unsigned int)tid + (unsigned int)(q * HALF);
         n = n < last_pair ? n : last_pair;
-        zfirst[q] = band_load2<BAND_INV_NTL != 0>((const char*)Z + (size_t)(n * 8u));
+        zfirst[q] = band_load2((const char*)Z + (size_t)(n * 8u));
     }
     band_ring_fill(img, ncomp, tabs, tab_slot, R);
     for (int i = tid; i < W; i += CT) {
@@ -1822,19 +1706,6 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
         const bool more = tile + (int)gridDim.x < ntiles;
         if (more) request(tile + gridDim.x, xfn, zinn);
         __builtin_amdgcn_sched_barrier(0);
-#if BAND_FEWI_STAGE == 2                                     /* (timing experiments: results wrong by construction) */
-        {
-#pragma unroll
-            for (int j = 0; j < FD; ++j)
-                if (j < nc)
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) {
-                        const unsigned int n = tbase + (unsigned int)(q * HALF);
-                        if (n + 1 < N32) band_store2<BAND_FEW_NT != 0>((char*)X + (int64_t)(kcol0 + j) * ldxb + (size_t)(n * 8u), zin[j][q].x + tabs[tid & 255], zin[j][q].y + etab[tid & 255]);
-                    }
-            continue;
-        }
-#endif
         double pend[NS][LAGE];
 #pragma unroll
         for (int l = 0; l < LAGE; ++l) {
@@ -1910,13 +1781,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
                         xlo[e] = band_lds_f64(xp - 8);
                         xhi[e] = band_lds_f64_single(xp);
                     }
-#if BAND_FEWI_STAGE == 3
-#pragma unroll
-                    for (int e = 0; e < NS; ++e) { r[e] = xlo[e] + ey[e].y; E[e] = xhi[e] * ey[e].x; }
-#else
 #pragma unroll
                     for (int e = 0; e < NS; ++e) interp(ey[e].y, xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
-#endif
                 }
                 if (outl != 0) {
                     // outliers (the tails of the table, NaN; every row of a degenerate table): clip as TM:4074-4076,
@@ -1947,7 +1813,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
                 for (int q = 0; q < NP; ++q) {
                     const unsigned int n = tbase + (unsigned int)(q * HALF);
                     char* xp = xcol + (size_t)(n * 8u);
-                    if (n + 1 < N32) band_store2<BAND_FEW_NT != 0>(xp, r[2 * q], r[2 * q + 1]);
+                    if (n + 1 < N32) band_store2<true>(xp, r[2 * q], r[2 * q + 1]);
                     else if (n < N32) *(double*)xp = r[2 * q];
                 }
             }
@@ -2172,7 +2038,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
                         if (Z) {
                             const unsigned int n = tbase + (unsigned int)(q * HALF);
                             char* zp = zcol + (size_t)(n * 8u);
-                            if (n + 1 < N32) band_store2<BAND_FEW_NT != 0>(zp, zv[0], zv[1]);
+                            if (n + 1 < N32) band_store2<true>(zp, zv[0], zv[1]);
                             else if (n < N32) *(double*)zp = zv[0];
                         }
                         __builtin_amdgcn_sched_barrier(0);
@@ -2309,7 +2175,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
                     for (int q = 0; q < NP; ++q) {
                         const unsigned int n = tbase + (unsigned int)(q * HALF);
                         char* xp = xcol + (size_t)(n * 8u);
-                        if (n + 1 < N32) band_store2<BAND_FEW_NT != 0>(xp, r[2 * q], r[2 * q + 1]);
+                        if (n + 1 < N32) band_store2<true>(xp, r[2 * q], r[2 * q + 1]);
                         else if (n < N32) *(double*)xp = r[2 * q];
                     }
                 }
@@ -2341,12 +2207,8 @@ static void allow_lds(const void* kern, size_t bytes) {
 // accesses are line-aligned (a chunk that starts inside a line makes every wave's store touch nine lines, two of them
 // partially: the column stream then runs at 72 % of the copy rate instead of ...: profiles/r03_*)
 static int64_t chunk_rows(int64_t N, int cus) {
-    static const int align = [] { const char* e = getenv("TTM_BAND_ROWALIGN"); int a = e ? atoi(e) : 32; return a < 2 ? 2 : a; }();
-    static const int forced = [] { const char* e = getenv("TTM_BAND_ROWS"); return e ? atoi(e) : 0; }();      // (tuning)
-    int64_t rows = (N + cus - 1) / cus;
-    rows = (rows + align - 1) / align * align;
-    if (forced > 0 && forced >= rows) rows = forced;
-    return rows;
+    const int64_t rows = (N + cus - 1) / cus;
+    return (rows + 31) / 32 * 32;
 }
 
 int record_stride(int cls, int lag) { return rec_stride(cls, lag); }
@@ -2430,8 +2292,7 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
     }
     lds += fixed - stat;                                      // (dynamic part)
     // log-determinant only: the derivative of a separable component is a function of its own column alone (k_band_logdet)
-    static const int ld_on = [] { const char* e = getenv("TTM_BAND_LOGDET"); return e ? atoi(e) : 1; }();
-    if (logdet && !Zsoa && !sumsq && ld_on && k1 - k0 <= BAND_UNI) {
+    if (logdet && !Zsoa && !sumsq && k1 - k0 <= BAND_UNI) {
         const size_t lbudget = lds_per_cu - (size_t)BAND_UNI * 8;
         int lblk = 0;
         int LBc = plan_blocks(p, k0, k1, lbudget, &lblk);
@@ -2469,8 +2330,7 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
     }
     const int cls = p->u_h_cls;
     // a few components: everything requested at once, tiles of 2048 rows (k_band_few)
-    static const int few_on = [] { const char* e = getenv("TTM_BAND_FEW"); return e ? atoi(e) : 1; }();
-    if (k1 - k0 <= TTM_P_FEW_D && few_on) {
+    if (k1 - k0 <= TTM_P_FEW_D) {
         // the splines of the sweep as they stand in the U section (padding between them included)
         int tab0 = p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_TAB_OFF];
         int ntab = p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_TAB_OFF] + TTM_U_TSTRIDE * p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_NI] - tab0;
@@ -2590,16 +2450,13 @@ int roundtrip(const ttm_program* p, const double* U, int k0, int k1, const doubl
     return 0;
 }
 
-static double window_fraction() {
-    static const double wfrac = [] { const char* e = getenv("TTM_BAND_WFRAC"); return e ? atof(e) : 0.52; }();
-    return wfrac;
-}
+constexpr double BAND_WFRAC = 0.52;                  /* fraction of a table's grid points a window keeps (k_inverse_rt) */
 
 // resident-table images (ttm_band_image.h) of the components [k0, k1) for this table geometry: the plan, or false
 bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, size_t lds_per_cu, int window, int block, int* w0, int* W, int* tab_slot) {
     if (!usable(p, k0, k1) || p->u_p_lag != 2 || k1 - k0 <= TTM_P_FEW_D) return false;
     BandRingPlan pl;
-    if (!band_ring_plan(T, nb, k1 - k0, lds_per_cu, window, block, window_fraction(), &pl)) return false;
+    if (!band_ring_plan(T, nb, k1 - k0, lds_per_cu, window, block, BAND_WFRAC, &pl)) return false;
     *w0 = pl.w0; *W = pl.W; *tab_slot = pl.tab_slot;
     return true;
 }
@@ -2616,8 +2473,7 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
     if (!aligned) return 1;
     const int ncomp = k1 - k0;
     // a few components: whole tables, everything requested at once, tiles of 2048 rows
-    static const int few_on = [] { const char* e = getenv("TTM_BAND_FEW"); return e ? atoi(e) : 1; }();
-    if (ncomp <= TTM_P_FEW_D && few_on && T + 4 <= BAND_CT && window <= 0) {          // (no blocks, no windows: `block` does not apply)
+    if (ncomp <= TTM_P_FEW_D && T + 4 <= BAND_CT && window <= 0) {          // (no blocks, no windows: `block` does not apply)
         const int Weven = (T + 4 + 1) & ~1;
         const int tab_slot = BAND_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1);
         const size_t lds = ((size_t)ncomp * tab_slot + (size_t)2 * Weven) * 8;
@@ -2646,11 +2502,9 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
         }
     }
     if (p->u_p_lag != 2 || p->u_h_cls > 3) return 1;       // (lag-3 records / order class 4: the few-component kernels only)
-    static const int stagger = [] { const char* e = getenv("TTM_BAND_STAGGER"); return e ? atoi(e) : 1; }();
-    const double wfrac = window_fraction();
     // resident-table images at hand (ttm_inverse_table_build_index wrote them): the ring kernel
     BandRingPlan pl;
-    if (img && (uintptr_t)img % 16 == 0 && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, wfrac, &pl) &&
+    if (img && (uintptr_t)img % 16 == 0 && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl) &&
         pl.tab_slot == img_doubles) {                         // (laid out for another plan - options changed in between: not this kernel)
         typedef void (*rkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, double*, int64_t, int64_t, const double*, int, double,
                                 double, double, const double*, const double*, const double*, int, int, int, int64_t, int, int);
@@ -2679,15 +2533,14 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
         if (Bc > ncomp) Bc = ncomp;
         if (Bc > BAND_RT_KMAX) Bc = BAND_RT_KMAX;
         if (block > 0 && block < Bc) Bc = block;
-        nblk = (ncomp + Bc - 1) / Bc;
-        if (!stagger) Bc = (ncomp + nblk - 1) / nblk;                     // even blocks (staggered: full blocks + a short one)
+        nblk = (ncomp + Bc - 1) / Bc;                                     // (full blocks + a short one: k_band_inverse staggers them)
         lds = fixed + (size_t)Bc * tab_slot * 8;
     };
     plan();
     // windowed tables when that saves a pass over the chunk (k_inverse_rt)
     if (window != 0 && (window > 0 || (Bc > 0 && nblk > 1))) {
         const int Bfull = Bc, nfull = nblk;
-        W = window > 0 ? (window < 16 ? 16 : window) : (int)(wfrac * T);
+        W = window > 0 ? (window < 16 ? 16 : window) : (int)(BAND_WFRAC * T);
         if (W >= T) W = T - 1;
         w0 = (T - W) / 2;
         plan();

@@ -29,9 +29,7 @@
 
 namespace ttm {
 
-#ifndef TTM_I_NODES
 #define TTM_I_NODES 5
-#endif
 
 #if defined(__HIPCC__)
 __device__ double g_mono_table[6 * (TTM_I_PMAX + 1) * (TTM_I_PMAX + 1)] = { TTM_MONO_TABLE_VALUES };   // (not const: scalar loads, see g_exp_coef)
@@ -219,25 +217,13 @@ TTM_HD void mon_eval(const Comp&, const Prog& p, const double& t, const DenseMon
 template <int PH, int PP, int RECT, bool DER, class XA, class Slots>
 TTM_HD void dense_sample_forward(const Comp& c, const Prog& p, double qw_sum, VarCache<XA, double>& x, Slots& w, bool want_value,
                                  double& S, double& dS) {
-#ifndef INT_X_NOW                                           /* (INT_X_*: timing experiments, results wrong by construction) */
     dense_weights<double>(c, p, x, w);
-#endif
     DenseMonoSet<PH, PP, RECT> s;
-#ifndef INT_X_NOMONO
     dense_monomials<PH, PP>(c, p, w, s.d);
-#else
-    for (int j = 0; j <= PH; ++j) s.d.h[j] = 0.01 * (j + 1);
-    for (int j = 0; j <= PP; ++j) s.d.a[j] = 0.02 * (j + 1);
-    s.d.probe = 0.0;
-#endif
     s.qw_sum = qw_sum;
     // (the nonmonotone part first: behind the node loop it would keep the component's table pointers alive across it)
     const double xk = x.get(c.kc);
-#ifndef INT_X_NONM
     const double nm = want_value ? nonmon_sum<double>(c, p, x) : 0.0;
-#else
-    const double nm = xk;
-#endif
     double m, dm;
     mon_eval<TTM_MONO_INTEGRATED, DER>(c, p, xk, s, m, dm);
     S = want_value ? nm + m : m;
@@ -386,10 +372,6 @@ inline bool dense_range_class(const int32_t* h_complex, int k0, int k1, DenseCla
 // run CALL(PH, PP, RECT) for the class and rectifier given at run time (host-side dispatch: kernel pick, test double)
 #define TTM_DENSE_DISPATCH_RECT(CALL, PH, PP, rect) \
     do { if ((rect) == TTM_RECT_EXPONENTIAL) { CALL(PH, PP, TTM_RECT_EXPONENTIAL); } else { CALL(PH, PP, -1); } } while (0)
-#ifdef TTM_INT_MINI      /* (tuning builds: two classes, exponential rectifier only - a sixth of the compile time) */
-#define TTM_DENSE_DISPATCH(CALL, cls, rect) \
-    do { if ((cls).ph == 3) { CALL(3, 0, TTM_RECT_EXPONENTIAL); } else { CALL(5, 0, TTM_RECT_EXPONENTIAL); } } while (0)
-#else
 #define TTM_DENSE_DISPATCH(CALL, cls, rect)                                           \
     do {                                                                               \
         if ((cls).pp == 0 && (cls).ph == 3) TTM_DENSE_DISPATCH_RECT(CALL, 3, 0, rect); \
@@ -399,6 +381,5 @@ inline bool dense_range_class(const int32_t* h_complex, int k0, int k1, DenseCla
         else if ((cls).ph == 0) TTM_DENSE_DISPATCH_RECT(CALL, 0, 10, rect);            \
         else TTM_DENSE_DISPATCH_RECT(CALL, 10, 10, rect);                              \
     } while (0)
-#endif
 
 }  // namespace ttm

@@ -271,11 +271,8 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#ifndef XOBJ_OCC
-#define XOBJ_OCC 1
-#endif
 template <int PH, int PP, int RECT, int NCH>
-__global__ __launch_bounds__(256, XOBJ_OCC) void k_int_objective(DevProg P, int k, XCoef hc, const double* __restrict__ d_coef, int ncoef,
+__global__ __launch_bounds__(256, 1) void k_int_objective(DevProg P, int k, XCoef hc, const double* __restrict__ d_coef, int ncoef,
                                                                  const double* __restrict__ X, int64_t ldx, int64_t N, int nfold, int ncols,
                                                                  double* __restrict__ partial, unsigned int* __restrict__ counter,
                                                                  double* __restrict__ out, double* flag, double mark) {
@@ -311,11 +308,7 @@ __global__ __launch_bounds__(256, XOBJ_OCC) void k_int_objective(DevProg P, int 
     }
     for (int i = tid; i < TTM_HOSTCOEF_MAX; i += bd) lcoef[i] = d_coef ? (i < ncoef ? d_coef[i] : 0.0) : hc.c[i];
     __syncthreads();
-#ifndef XOBJ_X_NOFOLD                                        /* (XOBJ_X_*: timing builds, results wrong by construction) */
     fold_coeffs(P.itab + off[k], P.ftab + off[4 * D1 + k], P.dpar + off[D1 + k], lcoef, lfold, tid, bd);
-#else
-    for (int i = tid; i < nfold; i += bd) lfold[i] = 0.01;
-#endif
     __syncthreads();
     WaveRow row{wblock + lane};
     for (int64_t n0 = (int64_t)blockIdx.x * bd; n0 < N; n0 += (int64_t)gridDim.x * bd) {
@@ -326,13 +319,8 @@ __global__ __launch_bounds__(256, XOBJ_OCC) void k_int_objective(DevProg P, int 
         // vector register across the whole loop)
         const double* fx = lfold + xp.fold_x;
         asm volatile("" : "+v"(fx));
-#ifndef XOBJ_X_NOROW
         xobj_sample_row<PH, PP, RECT>(xp, g, qws, fx, xa, row, active);
-#else
-        for (int c = 0; c < ncols; ++c) row.set(c, xa(xp.kc) + fx[c & 7]);
-#endif
         wave_lds_sync();
-#ifndef XOBJ_X_NOSUM
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             if (64 * c < nsum) {
@@ -342,9 +330,6 @@ __global__ __launch_bounds__(256, XOBJ_OCC) void k_int_objective(DevProg P, int 
                 for (int s = 0; s < 64; ++s) acc[c][s & 1] = fma(p1[s], p2[s], acc[c][s & 1]);
             }
         }
-#else
-        acc[0][0] += wblock[o1[0]] + wblock[o2[0]];
-#endif
         wave_lds_sync();
     }
 #pragma unroll
@@ -356,10 +341,6 @@ __global__ __launch_bounds__(256, XOBJ_OCC) void k_int_objective(DevProg P, int 
         coherent_store(partial + (int64_t)blockIdx.x * nsum + i, v);
     }
     drain_stores();
-#ifdef XOBJ_X_NOFIN
-    if (blockIdx.x == 0 && tid == 0) __hip_atomic_store(flag ? flag : out, mark, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    return;
-#endif
     {
         // (LDS: the rows are done with - group / final sums in `rows`, scratch of nw x nsum in the wave totals' place)
         double* fin = rows;                                       // sums of all workgroups, then the results behind them

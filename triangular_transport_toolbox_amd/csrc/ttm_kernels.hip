@@ -996,12 +996,7 @@ __global__ __launch_bounds__(256) void k_forward_u(const int* __restrict__ ucomp
 // Requires 16-byte aligned X / Z columns (even leading dimensions) and ldx >= N rounded up to even.
 // LDS (doubles): [x ring: (LEAD+1) x 512 | table ring: 3 x tab_slot | column cache: 2 x ways x 2 x 256]
 // ---------------------------------------------------------------------------
-#ifndef TTM_UL_CW
 #define TTM_UL_CW 4           // evaluating waves per workgroup
-#endif
-#ifndef TTM_FWD_ETAB          // tuning knob: which forward hot kernels take exp(-x^2/4) from the 2^(j/32) table
-#define TTM_FWD_ETAB(NS) false
-#endif
 #define TTM_UL_THREADS ((TTM_UL_CW + 2) * 64)
 #define TTM_UL_CT (TTM_UL_CW * 64)             // evaluating threads
 #define TTM_UL_ROWS (TTM_UL_CW * 128)          // rows per tile (evaluating waves x 64 lanes x 2 samples)
@@ -1010,12 +1005,8 @@ __global__ __launch_bounds__(256) void k_forward_u(const int* __restrict__ ucomp
 // more, smaller workgroups interleave better: 0.172 -> 0.162 ms at C5), four with the fused log-determinant (more
 // arithmetic per step; the per-step table is then shared by twice the rows).  The inverse stays at TTM_UL_CW (its
 // 12 KB table per step wants the larger tile).
-#ifndef TTM_HL_CW_PLAIN
 #define TTM_HL_CW_PLAIN 2
-#endif
-#ifndef TTM_HL_CW_LD
 #define TTM_HL_CW_LD 4
-#endif
 #define TTM_HL_FWD_CW(WANT_LD) ((WANT_LD) ? TTM_HL_CW_LD : TTM_HL_CW_PLAIN)
 #define TTM_HL_FWD_BOUNDS(WANT_LD) __launch_bounds__((TTM_HL_FWD_CW(WANT_LD) + 2) * 64)
 // xlead / tlead (kernel arguments): how many steps ahead of the evaluation the x / table loaders run; the rings have
@@ -1294,12 +1285,6 @@ __global__ TTM_HL_FWD_BOUNDS(WANT_LD) void k_forward_hl(const int* __restrict__ 
     Store cst;
     cst.base = cache + 2 * tid;
     cst.stride = CT;
-    if (TTM_FWD_ETAB(NS)) {                                              // 2^(j/32) table behind the column cache
-        double* etab = cache + (size_t)2 * ways * NS * CT;
-        if (tid < TTM_EXPQ_TABLE_LEN) etab[tid] = g_expq_table[tid];
-        cst.etab = etab;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // (barrier A(0) follows)
-    }
     const bool want_val = (Z != nullptr) || (sumsq != nullptr);
     bool act0[NP], act1[NP];
 #pragma unroll
@@ -1348,7 +1333,7 @@ __global__ TTM_HL_FWD_BOUNDS(WANT_LD) void k_forward_hl(const int* __restrict__ 
         xs = (xs + 1 == XSLOTS) ? 0 : xs + 1;
         ts = (ts + 1 == TSLOTS) ? 0 : ts + 1;
         R Sv, dS;
-        h_component<NG, DB, DA, GS, WANT_LD, TTM_FWD_ETAB(NS)>(rec, tab, xk, cst, WANT_LD ? want_val : true, Sv, dS);
+        h_component<NG, DB, DA, GS, WANT_LD>(rec, tab, xk, cst, WANT_LD ? want_val : true, Sv, dS);
         if (WANT_LD) ld += fast_log(dS);
         if (Z) {
             double* zt = Z + (int64_t)(k - k0) * ldz + ctile * ROWS + 2 * tid;
@@ -1889,21 +1874,10 @@ __global__ __launch_bounds__(1024) void k_inverse_rt(const int* __restrict__ uco
                 rec += HS; slot += tab_slot; zcol += ldzb;
             };
             int j = 0;
-#ifndef TTM_RT_UNPAIRED
             for (; j + 1 < nk; j += 2) {
                 step(j, bx1, be1, bx2, be2);
                 step(j + 1, bx2, be2, bx1, be1);
             }
-#else
-            for (; j + 1 < nk; ++j) {                                    // (tuning builds: the register shift per step)
-                step(j, bx1, be1, bx2, be2);
-#pragma unroll
-                for (int q = 0; q < NP; ++q) {
-                    const D2 tx = bx1[q], te = be1[q];
-                    bx1[q] = bx2[q]; be1[q] = be2[q]; bx2[q] = tx; be2[q] = te;
-                }
-            }
-#endif
             if (j < nk) {
                 step(j, bx1, be1, bx2, be2);
                 if (BAND) {                                              // odd number of steps: back to the canonical roles

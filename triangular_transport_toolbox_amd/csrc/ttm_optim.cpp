@@ -245,11 +245,6 @@ int ttm_lbfgsb_minimize(int32_t n, double* x, const double* lb, const double* ub
 
 namespace {
 
-bool closed_form_enabled() {
-    static const bool closed = [] { const char* e = getenv("TTM_SEP_CLOSED_FORM"); return !e || atoi(e) != 0; }();
-    return closed;
-}
-
 // The checks every entry point of the separable loops makes before anything is launched or indexed.  A task evaluates from the
 // cached derivative basis (dPsi) or recomputes it from the x_k column (xk, kinds, pars).
 int check_task(const ttm_sep_task& q, int64_t N, double Ntotal, const double* sums_dev, const ttm_comm* comm) {
@@ -402,7 +397,7 @@ int run_task(ttm_sep_task& q, int64_t N, double Ntotal, double delta, double* su
         double Nw, KN;                                       // closed form of m = 1: weights N, sum_n log dPsi_n
         int rc;
     } L{{q, N, delta, sums_dev, comm, stream}, q, 1.0 / Ntotal, delta, pre_x,
-        q.dPsi && closed_form_enabled() && q.m == 1 && delta >= 0.0 && q.lb && q.lb[0] >= 0.0, false, 0.0, 0.0, 0};
+        q.dPsi && q.m == 1 && delta >= 0.0 && q.lb && q.lb[0] >= 0.0, false, 0.0, 0.0, 0};
     const int key = L.ev.choose(pre_x != nullptr);
     auto fun = [](int32_t n, const double* cc, double* f, double* g, void* user) -> int32_t {
         Loop& L = *(Loop*)user;
@@ -465,7 +460,7 @@ int ttm_optimize_separable_batch(ttm_sep_task* tasks, int32_t ntasks, int64_t N,
     std::vector<int> ahead, rest;
     for (int t = 0; t < ntasks; ++t) {
         const ttm_sep_task& q = tasks[t];
-        const bool one = q.dPsi && q.m == 1 && closed_form_enabled() && delta >= 0.0 && check_task(q, N, Ntotal, nullptr, nullptr) == TTM_OK &&
+        const bool one = q.dPsi && q.m == 1 && delta >= 0.0 && check_task(q, N, Ntotal, nullptr, nullptr) == TTM_OK &&
                          q.lb && q.lb[0] >= 0.0;
         (one ? ahead : rest).push_back(t);
     }

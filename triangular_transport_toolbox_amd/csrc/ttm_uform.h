@@ -515,15 +515,6 @@ TTM_HD void u_spline_eval(const SplineIdx<R>& ix, const SplineRegs<H>& q, R& g, 
     for (int e = 0; e < H; ++e) { set_elem(g, E0 + e, a[e]); set_elem(dg, E0 + e, da[e]); }
 }
 
-// Scheduling fences between the phases (tuning knob, off): with them a lone workgroup evaluates 13 % faster (every
-// LDS latency is behind arithmetic), but next to the loader waves and the per-step barrier the kernel is slower
-// (0.22 against 0.17 ms at C5) - the waves of a workgroup then all want the LDS, then all the VALU, at the same time.
-#if defined(__HIP_DEVICE_COMPILE__) && defined(TTM_HL_PHASES)
-#define TTM_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)      // nothing is scheduled across this point
-#else
-#define TTM_SCHED_FENCE() ((void)0)
-#endif
-
 // S_k and dS_k/dx_k of one component in U-form; afterwards x_k (and exp(-x_k^2/4) when a later group reads it)
 // goes into its planned cache slot.  x: a PlanCache.
 template <int DB, int DA, bool DER, class R, class Fetch>
@@ -562,7 +553,9 @@ TTM_HD void u_component(cint_p uc, cint_p ug_all, cdbl_p U, const double* tab, c
 // loads of the step are at fixed offsets from `rec`.  A component that uses all NG records, has a spline and
 // stores exp(-x_k^2/4) - every component of a banded map but the first and last few - runs as ONE basic block, so
 // the scheduler can overlap the cache / table reads with the exp and Horner chains; the others take the guarded path.
-template <int NG, int DB, int DA, int GS, bool DER, bool ETAB = false, class R, class ST>
+// (No scheduling fences between its phases: a lone workgroup gains 13 %, but beside the loader waves and the per-step
+// barrier the kernel is slower, 0.22 against 0.17 ms at C5 - the waves then all want the LDS, then all the VALU.)
+template <int NG, int DB, int DA, int GS, bool DER, class R, class ST>
 TTM_HD void h_component(cdbl_p rec, const double* tab, const R& xk, const ST& st, bool want_value, R& S, R& dS) {
     cint_p ri = (cint_p)rec;
     const int put2 = ri[0], flg = ri[1], nI = ri[2], n_grp = ri[13];
@@ -579,17 +572,12 @@ TTM_HD void h_component(cdbl_p rec, const double* tab, const R& xk, const ST& st
         u_spline_index(nI, rec[3], rec[4], xk, ix);
         SplineRegs<H> q;
         u_spline_gather<0, H>(tab, ix, q);
-        TTM_SCHED_FENCE();
         // phase 2: arithmetic that needs none of them (the exp of the column cache) behind their latency
-        const R ek = (ETAB ? exp_q_tab(st.etab, xk) : exp_q_fast(xk));
-        TTM_SCHED_FENCE();
+        const R ek = exp_q_fast(xk);
         // phase 3: spline of the first half; then the second half's gather behind the groups
         R m, dm(0.0);
         u_spline_eval<0, H, DER>(ix, q, m, dm);
-        if (L > 1) {
-            TTM_SCHED_FENCE();
-            u_spline_gather<(L > 1 ? H : 0), H>(tab, ix, q);
-        }
+        if (L > 1) u_spline_gather<(L > 1 ? H : 0), H>(tab, ix, q);
         R s(rec[2]);
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
@@ -599,10 +587,7 @@ TTM_HD void h_component(cdbl_p rec, const double* tab, const R& xk, const ST& st
             u_horner_fixed<DA, false>(gr + 2 + DB, xv[g], a, dv);
             s = vfma(ev[g], b, s) + a;
         }
-        if (L > 1) {
-            TTM_SCHED_FENCE();
-            u_spline_eval<(L > 1 ? H : 0), H, DER>(ix, q, m, dm);
-        }
+        if (L > 1) u_spline_eval<(L > 1 ? H : 0), H, DER>(ix, q, m, dm);
         if (DER) dm = dm * rec[5];
         S = s + m;
         dS = dm;
@@ -626,7 +611,7 @@ TTM_HD void h_component(cdbl_p rec, const double* tab, const R& xk, const ST& st
         }
     }
     R ek(0.0);
-    if (flg & 1) ek = (ETAB ? exp_q_tab(st.etab, xk) : exp_q_fast(xk));
+    if (flg & 1) ek = exp_q_fast(xk);
     R m(0.0), dm(0.0);
     if (nI > 0) u_spline<DER>(tab, nI, rec[3], rec[4], rec[5], xk, m, dm);
     S = s + m;

@@ -166,9 +166,7 @@ TTM_HD double xprog_sample_root(const XProg& xp, const Prog& p, double qw_sum, F
     return NEWTON ? sample_newton<TTM_MONO_INTEGRATED>(unused, p, off, zk, s, it) : sample_bisect<TTM_MONO_INTEGRATED>(unused, p, off, zk, s, cap, it);
 }
 
-#ifndef XOBJ_NODES
 #define XOBJ_NODES 4          /* nodes per pass of the objective's node loop: 115-123 vector registers (four waves per SIMD); 5: 125-134 */
-#endif
 // The row of one sample for the objective + gradient sums (see the head of this file).  active = false (a lane beyond the
 // ensemble, evaluated on a clamped sample): S, J and the q columns are zero, so the row adds nothing to any sum.
 template <int PH, int PP, int RECT, class FP, class XA, class Row>
