@@ -359,9 +359,9 @@ int  ttm_version(void);
 const char* ttm_last_kernel(void);
 /* Launch-planning options (tests and tuning runs): which kernel variant an entry point picks is normally decided from
  * the program and the ensemble size; an option pins one aspect of that choice, e.g. ttm_set_option("no_uform", 1),
- * ("forward_ns", 2), ("rt_off", 1) - the list is TTM_OPTIONS in csrc/ttm_kernels.hip.  Defaults come from the environment
- * variables TTM_<NAME>, read once when the library is first used (never on the launch path); ttm_reset_options() goes
- * back to them.  Options change speed and kernel choice only, never results beyond the documented tolerances.       */
+ * ("forward_ns", 2), ("rt_off", 1) - the list is TTM_OPTIONS in csrc/ttm_options.h; any other name is TTM_E_ARG.  Every
+ * process starts from the compiled defaults (the environment plays no part); ttm_reset_options() goes back to them.
+ * Options change speed and kernel choice only, never results beyond the documented tolerances.                      */
 int ttm_set_option(const char* name, int32_t value);
 int ttm_reset_options(void);
 /* sizeof(ttm_program) as the library was compiled: bindings check their mirror of the struct against it */

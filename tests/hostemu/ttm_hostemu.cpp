@@ -20,10 +20,15 @@
 #include "../../triangular_transport_toolbox_amd/csrc/ttm_xprog.h"
 #include "../../triangular_transport_toolbox_amd/csrc/ttm_uform.h"
 #include "../../triangular_transport_toolbox_amd/csrc/ttm_rng.h"
+#include "../../triangular_transport_toolbox_amd/csrc/ttm_options.h"
 
 using namespace ttm;
 
 namespace {
+
+// the options (csrc/ttm_options.h): the test double reads those that choose between evaluators it has (no_plan, no_uform,
+// u_no_hot, int_dense, int_xprog); the others choose device kernel variants and are accepted and ignored
+Tuning g_tuning;
 
 struct VecSlots {
     double* base;
@@ -81,14 +86,14 @@ void comp_of(const ttm_program* p, int k, const double* coef_k, HostComp& h, con
 // same dispatch rule as the library (csrc/ttm_int.hip: ttm_int::usable): integrated maps whose components all have a dense
 // B set go through the monomial-form bodies of csrc/ttm_dense.h
 bool int_dense(const ttm_program* p, int ka, int kb, DenseClass& cls) {
-    if (getenv("TTM_INT_DENSE") && atoi(getenv("TTM_INT_DENSE")) == 0) return false;
+    if (g_tuning.int_dense == 0) return false;
     if (p->monotonicity != TTM_MONO_INTEGRATED || p->family < 0 || p->family > 5) return false;
     return dense_range_class(p->h_complex, ka, kb, cls);
 }
 
 // same dispatch rule as the library (csrc/ttm_int.hip: xprog_rows): the X-program kernels when every component of the range has one
 bool all_xprog(const ttm_program* p, int ka, int kb) {
-    if (getenv("TTM_INT_XPROG") && atoi(getenv("TTM_INT_XPROG")) == 0) return false;
+    if (g_tuning.int_xprog == 0) return false;
     for (int k = ka; k < kb; ++k)
         if (!(p->h_complex[k] & 16)) return false;
     return true;
@@ -96,7 +101,7 @@ bool all_xprog(const ttm_program* p, int ka, int kb) {
 
 // same dispatch rule as the library: planned-cache fast path when every component of the range is simple
 bool all_fast(const ttm_program* p, int ka, int kb) {
-    if (getenv("TTM_NO_PLAN")) return false;
+    if (g_tuning.no_plan) return false;
     for (int k = ka; k < kb; ++k)
         if (p->h_complex[k] & 1) return false;
     return true;
@@ -134,18 +139,12 @@ void forward_u(const ttm_program* p, const double* fold, const XA& xa, int k0, i
     PlanCache<XA, R> x(xa, CacheStore<R>{cbuf, 1});
     if (k0 > 0) x.warm(p->ucomp + TTM_UC_STATE(p->D, k0));
     ld = R(0.0); ss = R(0.0);
-    const bool fixed = getenv("TTM_EMU_U_FIXED") != nullptr;      // test knob: the fixed-degree instantiation
     for (int k = k0; k < k1; ++k) {
         const int* uc = p->ucomp + k * TTM_UC_LEN;
         const R xk = xa(uc[TTM_UC_KC]);
         R S, dS;
-        if (fixed) {
-            if (want_ld) u_component<TTM_U_PMAX, TTM_U_PMAX, true>(uc, p->ugrp, U, U + uc[TTM_UC_TAB_OFF], xk, x, want_val, S, dS);
-            else u_component<TTM_U_PMAX, TTM_U_PMAX, false>(uc, p->ugrp, U, U + uc[TTM_UC_TAB_OFF], xk, x, true, S, dS);
-        } else {
-            if (want_ld) u_component<-1, -1, true>(uc, p->ugrp, U, U + uc[TTM_UC_TAB_OFF], xk, x, want_val, S, dS);
-            else u_component<-1, -1, false>(uc, p->ugrp, U, U + uc[TTM_UC_TAB_OFF], xk, x, true, S, dS);
-        }
+        if (want_ld) u_component<-1, -1, true>(uc, p->ugrp, U, U + uc[TTM_UC_TAB_OFF], xk, x, want_val, S, dS);
+        else u_component<-1, -1, false>(uc, p->ugrp, U, U + uc[TTM_UC_TAB_OFF], xk, x, true, S, dS);
         if (want_ld) ld += fast_log(sigma ? fast_div(dS, sigma[k - k0]) : dS);
         S_out[k - k0] = S;
         ss = vfma(S, S, ss);
@@ -203,15 +202,14 @@ const char* ttm_last_error_string(void) { return "hostemu"; }
 int ttm_set_error_string(const char*) { return TTM_OK; }
 int ttm_version(void) { return TTM_VERSION; }
 const char* ttm_last_kernel(void) { return "hostemu"; }
-// options of the test double: the three it knows live in its environment variables (read per call)
+// the library's option table (csrc/ttm_options.h): the same names, TTM_E_ARG for any other
 int ttm_set_option(const char* name, int32_t value) {
-    if (!name) return TTM_E_ARG;
-    const char* env = !strcmp(name, "no_plan") ? "TTM_NO_PLAN" : !strcmp(name, "no_uform") ? "TTM_NO_UFORM" :
-                      !strcmp(name, "u_no_hot") ? "TTM_EMU_NO_HOT" : nullptr;
-    if (env) { if (value) setenv(env, "1", 1); else unsetenv(env); }
-    return TTM_OK;                                  // (the other options select device kernel variants: nothing to do)
+    int* field = name ? tuning_field(g_tuning, name) : nullptr;
+    if (!field) return TTM_E_ARG;
+    *field = (int)value;
+    return TTM_OK;
 }
-int ttm_reset_options(void) { unsetenv("TTM_NO_PLAN"); unsetenv("TTM_NO_UFORM"); unsetenv("TTM_EMU_NO_HOT"); return TTM_OK; }
+int ttm_reset_options(void) { g_tuning = Tuning{}; return TTM_OK; }
 
 // the collective of the path (include/ttm.h "C1"): the test double has no RCCL; the harness registers a callback that
 // performs the reduction on the host buffer (tests: torch.distributed over gloo), so the class under test goes
@@ -368,7 +366,7 @@ int ttm_order_statistics_dist(const double* col, int64_t N, const int64_t* ranks
 }
 
 static int64_t fold_base_size(const ttm_program* p) { return ((int64_t)p->h_fold_off[p->D] + 8 + 1) & ~(int64_t)1; }
-static bool u_on(const ttm_program* p) { return p->u_enabled && !getenv("TTM_NO_UFORM"); }
+static bool u_on(const ttm_program* p) { return p->u_enabled && !g_tuning.no_uform; }
 static int plan_ways_of(const ttm_program* p) { return (p->plan_ways < 1 || p->plan_ways > TTM_PLAN_WAYS) ? TTM_PLAN_WAYS : p->plan_ways; }
 
 int64_t ttm_fold_size(const ttm_program* p) { return fold_base_size(p) + (p->u_enabled ? p->u_size : 0); }
@@ -416,7 +414,7 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
     const Prog g = make_prog(p);
     if (p->monotonicity == TTM_MONO_SEPARABLE && u_on(p) && all_fast(p, k0, k1)) {     // same dispatch as the library
         std::vector<double> S(k1 - k0);
-        const bool hot = p->u_h_cls > 0 && p->u_p_lag <= 2 && !getenv("TTM_EMU_NO_HOT");     // hot records (what k_forward_hl evaluates)
+        const bool hot = p->u_h_cls > 0 && p->u_p_lag <= 2 && !g_tuning.u_no_hot;     // hot records (what k_forward_hl evaluates)
         for (int64_t n = 0; n < N; ++n) {
             XSoA xa{X, ldx, n};
             double ld, ss;
@@ -541,7 +539,7 @@ int emu_forward_vec2(const ttm_program* p, const double* coef, const double* fol
             const int64_t n1 = n + 1 < N ? n + 1 : n;
             XSoA2 xa{X, ldx, n, n1};
             VecD<2> ld, ss;
-            const bool hot = p->u_h_cls > 0 && p->u_p_lag <= 2 && !getenv("TTM_EMU_NO_HOT");
+            const bool hot = p->u_h_cls > 0 && p->u_p_lag <= 2 && !g_tuning.u_no_hot;
             if (!(hot && forward_h_dispatch<VecD<2>>(p, fold, xa, k0, k1, true, true, S.data(), ld, ss, nullptr)))
                 forward_u<VecD<2>>(p, fold, xa, k0, k1, true, true, S.data(), ld, ss, nullptr);
             for (int k = k0; k < k1; ++k) {
@@ -651,7 +649,7 @@ int ttm_objective(const ttm_program* p, int32_t k, const double* coef_k, const d
     const double qws = dense ? dense_qw_sum(g) : 0.0;
     XProg xp;
     if (dense && xprog_view(p->itab + p->h_comp_off[k], p->dpar + p->h_dpar_off[k], xp) &&
-        !(getenv("TTM_INT_XPROG") && atoi(getenv("TTM_INT_XPROG")) == 0)) {
+        g_tuning.int_xprog != 0) {
         // the X-program path of csrc/ttm_int.hip (k_int_objective): a row per sample, every sum a product of four row
         // entries - the kernel gives a sum to a lane and walks the rows of a wave; here the same products in sample order
         const double* fx = c.fold + xp.fold_x;                  // (comp_of folded the recipe, X section included)
@@ -867,7 +865,7 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
                       int32_t truncate, const double*, int64_t, void*) {
     const Prog g = make_prog(p);
     if (u_on(p) && p->u_h_cls >= 1 && p->u_h_cls <= 3 && p->u_p_lag <= 2 && (p->u_h_ng == 2 || p->u_h_ng == 4) && all_fast(p, k0, k1) && h_y_affine && ldy == 0 &&
-        (nb + 1) % 4 == 0 && !getenv("TTM_EMU_NO_HOT")) {
+        (nb + 1) % 4 == 0 && !g_tuning.u_no_hot) {
         // hot records + bucket scan + computed linspace abscissae: what k_inverse_hl evaluates
         const double* U = fold + fold_base_size(p);
         const int cls = p->u_h_cls, ng = p->u_h_ng;
@@ -972,7 +970,7 @@ int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* f
             VecSlots w{scr.data()};
             int it = 0;
             double r = 0.0;
-            if (dense && all_xprog(p, k0, k1) && getenv("TTM_INT_XPROG") && atoi(getenv("TTM_INT_XPROG")) == 2) {
+            if (dense && all_xprog(p, k0, k1) && g_tuning.int_xprog == 2) {
                 XProg xp;
                 xprog_view(p->itab + p->h_comp_off[k], p->dpar + p->h_dpar_off[k], xp);
                 const double* fx = c.fold + xp.fold_x;
@@ -1017,7 +1015,7 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
             VecSlots w{scr.data()};
             int it = 0;
             double r = 0.0;
-            if (dense && all_xprog(p, k0, k1) && getenv("TTM_INT_XPROG") && atoi(getenv("TTM_INT_XPROG")) == 2) {
+            if (dense && all_xprog(p, k0, k1) && g_tuning.int_xprog == 2) {
                 XProg xp;
                 xprog_view(p->itab + p->h_comp_off[k], p->dpar + p->h_dpar_off[k], xp);
                 const double* fx = c.fold + xp.fold_x;

@@ -589,3 +589,34 @@ def test_roundtrip_in_one_launch_equals_forward_then_inverse(case, ttm_opt):
     ttm_opt('roundtrip_fused', 0)
     Z3, X3, _, _, k3 = one_call(False)
     assert not k3.startswith('k_band_few_roundtrip') and same(Z3, Z2) and same(X3, X2)
+
+
+@pytest.mark.gpu
+def test_option_names_in_the_environment_do_not_change_the_kernel_choice(tmp_path):
+    """Options are set through ttm_set_option only: TTM_BAND_FWD=0, TTM_NO_UFORM=1 and TTM_RT_OFF=1 in the environment of a fresh
+    process leave the forward map and the table inverse of a banded map (C5 at N = 100 000) on the kernels they take without them."""
+    import os
+    import subprocess
+    import sys
+    script = (
+        "import ctypes, sys\n"
+        "sys.path.insert(0, %r)\n"
+        "from tests.test_full_size import build\n"
+        "tm, om, X = build('C5', 'c5_sep', 100000)\n"
+        "tm._lib.ttm_last_kernel.restype = ctypes.c_char_p\n"
+        "tm.map(X[:1000])\n"
+        "tm.forward_device(tm._Xs, tm._N)\n"
+        "names = [tm._lib.ttm_last_kernel().decode()]\n"
+        "tm.inverse_device(tm._cols(tm.D, tm._N, zero=True), tm._N)\n"
+        "names.append(tm._lib.ttm_last_kernel().decode())\n"
+        "print(' '.join(names))\n"
+    ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = {}
+    for tag, extra in (('plain', {}), ('env', {'TTM_BAND_FWD': '0', 'TTM_NO_UFORM': '1', 'TTM_RT_OFF': '1'})):
+        env = {k: v for k, v in os.environ.items() if k not in ('TTM_BAND_FWD', 'TTM_NO_UFORM', 'TTM_RT_OFF')}
+        env.update(extra)
+        res = subprocess.run([sys.executable, '-c', script], env=env, capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, res.stderr[-2000:]
+        out[tag] = res.stdout.split()[-2:]
+    assert out['plain'][0] == 'k_band_forward' and out['plain'][1].startswith('k_band_inverse'), out['plain']
+    assert out['env'] == out['plain']

@@ -3,6 +3,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from triangular_transport_toolbox_amd import _capi, build
 
 
@@ -49,3 +51,26 @@ def test_host_double_exports_same_abi():
     lib = emu.lib()
     for name in declared_symbols():
         assert hasattr(lib, name), name
+
+
+def option_defaults():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, 'triangular_transport_toolbox_amd', 'csrc', 'ttm_options.h')).read()
+    return [(name.encode(), int(dflt)) for name, dflt in re.findall(r'^\s*X\((\w+), (-?\d+)\)', text, flags=re.M)]
+
+
+@pytest.mark.parametrize('backend', ['hostemu', pytest.param('hip', marks=pytest.mark.gpu)])
+def test_both_libraries_accept_the_same_option_names(backend):
+    """ttm_set_option takes every name of csrc/ttm_options.h and rejects any other with TTM_E_ARG - a misspelt name, or an option
+    that was removed (u_xlead) - on the host test double and on the device library alike."""
+    from tests.hostemu import emu
+    lib = emu.lib() if backend == 'hostemu' else _capi.load()
+    names = option_defaults()
+    assert len(names) >= 20 and (b'band_fwd', -1) in names
+    try:
+        for name, dflt in names:
+            assert lib.ttm_set_option(name, dflt) == 0, name
+        assert lib.ttm_set_option(b'band_fdw', 0) == -1            # (TTM_E_ARG)
+        assert lib.ttm_set_option(b'u_xlead', 2) == -1
+    finally:
+        lib.ttm_reset_options()

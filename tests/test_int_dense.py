@@ -1,13 +1,11 @@
 """The dense integrated-rectifier path (csrc/ttm_dense.h bodies, csrc/ttm_int.hip kernels: monomial form of g, Horner per
 quadrature node) against the generic evaluators it replaces (option int_dense = 0) and against the reference goldens, on
 both backends; on the GPU the kernels are asserted by name."""
-import os
-
 import numpy as np
 import pytest
 
 from tests.hostemu import emu
-from tests.util import INTEGRATED, case_X, check, coeff_lists, ctor_kwargs, load_case, make_oracle, relerr
+from tests.util import INTEGRATED, case_X, check, coeff_lists, ctor_kwargs, load_case, make_oracle, options, relerr
 
 
 @pytest.fixture(params=[pytest.param('hostemu'), pytest.param('hip', marks=pytest.mark.gpu)])
@@ -19,22 +17,9 @@ def backend(request):
         yield 'hip'
 
 
-class generic_path:
-    """int_dense = 0 for the duration of the block (library option on the GPU, environment switch of the test double)."""
-    def __init__(self, tm, backend):
-        self.tm, self.backend = tm, backend
-
-    def __enter__(self):
-        if self.backend == 'hip':
-            self.tm._lib.ttm_set_option(b'int_dense', 0)
-        else:
-            os.environ['TTM_INT_DENSE'] = '0'
-
-    def __exit__(self, *exc):
-        if self.backend == 'hip':
-            self.tm._lib.ttm_reset_options()
-        else:
-            del os.environ['TTM_INT_DENSE']
+def generic_path(tm):
+    """int_dense = 0 for the duration of the block (on the library the map runs on: device library or test double)."""
+    return options(tm._lib, int_dense=0)
 
 
 def make_tm(name, npz, desc, **extra):
@@ -80,7 +65,7 @@ def test_dense_and_generic_paths_agree(backend, name):
     tm.root_finder = 'newton'
     Xn = tm.inverse_map(Zin)
     tm.root_finder = 'reference'
-    with generic_path(tm, backend):
+    with generic_path(tm):
         Zg = tm.map(X)
         if backend == 'hip':
             tm.forward_device(tm._Xs, tm._N)
@@ -147,7 +132,7 @@ def test_example01_order10_map_takes_the_dense_kernels(backend):
         if backend == 'hip':
             tm._device_sums(k, c)
             assert last_kernel(tm) == 'k_int_objective'
-        with generic_path(tm, backend):
+        with generic_path(tm):
             tm._obj_cache = None
             Jg, Gg = tm.objective_function(c, k, div), tm.objective_function_jacobian(c, k, div)
             if backend == 'hip':
@@ -157,22 +142,9 @@ def test_example01_order10_map_takes_the_dense_kernels(backend):
         check('dense/gradient_vs_generic[ex01_order10]', relerr(G, Gg), 1e-11, backend)
 
 
-class walk_path:
+def walk_path(tm):
     """int_xprog = 0 for the duration of the block: the kernels that walk the term tables per sample."""
-    def __init__(self, tm, backend):
-        self.tm, self.backend = tm, backend
-
-    def __enter__(self):
-        if self.backend == 'hip':
-            self.tm._lib.ttm_set_option(b'int_xprog', 0)
-        else:
-            os.environ['TTM_INT_XPROG'] = '0'
-
-    def __exit__(self, *exc):
-        if self.backend == 'hip':
-            self.tm._lib.ttm_reset_options()
-        else:
-            del os.environ['TTM_INT_XPROG']
+    return options(tm._lib, int_xprog=0)
 
 
 @pytest.mark.parametrize('name', DENSE + ['ex01_order10'])
@@ -213,18 +185,9 @@ def test_x_program_and_term_table_walk_agree(backend, name):
                 tm._device_sums(k, c)
                 assert last_kernel(tm) == names[2]
         return out
-    if backend == 'hip':
-        tm._lib.ttm_set_option(b'int_xprog', 2)          # (the root searches through the X programs as well: off by default)
-    else:
-        os.environ['TTM_INT_XPROG'] = '2'
-    try:
+    with options(tm._lib, int_xprog=2):                    # (the root searches through the X programs as well: off by default)
         a = everything(('k_int_forward', 'k_int_root_x<bisect>', 'k_int_objective'))
-    finally:
-        if backend == 'hip':
-            tm._lib.ttm_reset_options()
-        else:
-            del os.environ['TTM_INT_XPROG']
-    with walk_path(tm, backend):
+    with walk_path(tm):
         b = everything(('k_int_forward<walk>', 'k_int_root<bisect>', 'k_int_objective_walk'))
     with np.errstate(all='ignore'):
         check('xprog/map_vs_walk[%s]' % name, relerr(a['Z'], b['Z']), 1e-12, backend)

@@ -1,16 +1,16 @@
 """
 The statically planned column cache of the fast kernels (termtable._plan_column_cache, PlanCache in
 csrc/ttm_eval.h): the plan is replayed in Python to check its invariants, and the planned evaluator is
-compared with the run-time tagged one (TTM_NO_PLAN) and on sweeps that start in the middle of the map
+compared with the run-time tagged one (option no_plan) and on sweeps that start in the middle of the map
 (conditional inverse / component shards), where the recorded entry state has to be preloaded.
 """
-import os
-
 import numpy as np
 import pytest
 
+from tests.hostemu import emu
 from tests.hostemu.emu import EmuMap
 from tests.test_hostemu_vs_oracle import build
+from tests.util import options
 from triangular_transport_toolbox_amd import specs, termtable
 
 FD = termtable.FD_LEN
@@ -96,16 +96,10 @@ def test_planned_equals_tagged_and_partial_sweeps(name):
     rng = np.random.default_rng(5)
     X = rng.standard_normal((64, cm.d_cols))
     # direct kernels (U-form off): statically planned column cache == run-time tagged cache, bit for bit
-    os.environ['TTM_NO_UFORM'] = '1'
-    try:
+    with options(emu.lib(), no_uform=1):
         Zd, ldd = _run(em, coef, X)
-        os.environ['TTM_NO_PLAN'] = '1'
-        try:
-            Zt, ldt = _run(em, coef, X)
-        finally:
-            del os.environ['TTM_NO_PLAN']
-    finally:
-        del os.environ['TTM_NO_UFORM']
+    with options(emu.lib(), no_uform=1, no_plan=1):
+        Zt, ldt = _run(em, coef, X)
     assert np.array_equal(Zd, Zt) and np.array_equal(ldd, ldt)
     # default dispatch (U-form when the map has one): same values to rounding, same planned cache
     Zp, ldp = _run(em, coef, X)

@@ -4,14 +4,12 @@ agreement with the direct evaluation and with the oracle, and the fall-backs (to
 rejected fit).  Runs on the host test double (same builder / evaluator bodies as the kernels) and, marked
 `gpu`, through libttm.so.
 """
-import os
-
 import numpy as np
 import pytest
 
 from tests.hostemu import emu
 from tests.test_hostemu_vs_oracle import build
-from tests.util import SEPARABLE, case_X, coeff_lists, ctor_kwargs, load_case, make_oracle, relerr
+from tests.util import SEPARABLE, case_X, coeff_lists, ctor_kwargs, load_case, make_oracle, options, relerr
 from triangular_transport_toolbox_amd import specs, termtable
 
 U_CASES = ['c2b_sep', 'c3_sep', 'c5_sep']
@@ -64,21 +62,15 @@ def test_fit_errors_and_direct_agreement(name):
     X = np.vstack((om.X[:300], rng.standard_normal((200, cm.d_cols)) * 3.0,      # far tails: the linear spline columns
                    rng.standard_normal((20, cm.d_cols)) * 30.0))
     Zu, ldu = em.forward(coef, X)
-    os.environ['TTM_NO_UFORM'] = '1'
-    try:
+    with options(emu.lib(), no_uform=1):
         Zd, ldd = em.forward(coef, X)
-    finally:
-        del os.environ['TTM_NO_UFORM']
     assert relerr(Zu, Zd) < 1e-12
     ok = np.isfinite(ldd)
     assert np.array_equal(np.isfinite(ldu), ok) and relerr(ldu[ok], ldd[ok]) < 1e-10
     # generic U-form evaluator (per-group degrees) == hot records (fixed degrees), where the map has them
     if cm.u_h_cls:
-        os.environ['TTM_EMU_NO_HOT'] = '1'
-        try:
+        with options(emu.lib(), u_no_hot=1):
             Zg, ldg = em.forward(coef, X)
-        finally:
-            del os.environ['TTM_EMU_NO_HOT']
         assert np.array_equal(Zg, Zu) and np.array_equal(ldg[ok], ldu[ok])
 
 

@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite: golden fixture loading and oracle construction."""
+import contextlib
 import json
 import os
 
@@ -12,6 +13,18 @@ ALL_CASES = ['c1_int', 'c2a_int', 'c2b_sep', 'c3_sep', 'c3_int', 'c5_sep', 'c5_i
              'misc_family_chebyshev', 'misc_family_laguerre', 'misc_family_legendre']
 INTEGRATED = [c for c in ALL_CASES if c.endswith('_int') or c == 'misc_grid' or c.startswith('misc_family')]
 SEPARABLE = ['c2b_sep', 'c3_sep', 'c5_sep', 'misc_sep', 'ex03_order10']
+
+
+@contextlib.contextmanager
+def options(lib, **values):
+    """Launch-planning options (include/ttm.h: ttm_set_option) of `lib` - the device library or the host test double - for the
+    duration of the block; every option goes back to its default afterwards."""
+    try:
+        for name, value in values.items():
+            assert lib.ttm_set_option(name.encode(), value) == 0, name
+        yield
+    finally:
+        lib.ttm_reset_options()
 
 
 def load_case(name):

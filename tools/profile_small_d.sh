@@ -1,7 +1,7 @@
 #!/bin/bash
 # Kernel durations of the small-D configurations (C2b at N = 1e6, C3 at N = 5e5) from the kernel trace: the launches of
 # these configurations are shorter than a Python call, so event timing around a Python loop measures the host.
-# usage: tools/profile_small_d.sh [tag]      (environment, e.g. TTM_U_LOADER=1, is passed on)
+# usage: tools/profile_small_d.sh [tag]      (default launch planning; pin an option with _capi.set_option in tools/small_d.py)
 R=${GRAFT_REPO_ROOT:-$PWD}
 TAG=${1:-sd}
 cd /tmp && export TMPDIR=/tmp

@@ -33,6 +33,7 @@
 #include "ttm_band.h"
 #include "ttm_band_image.h"
 #include "ttm_int.h"
+#include "ttm_options.h"
 
 using namespace ttm;
 
@@ -2858,8 +2859,7 @@ __global__ __launch_bounds__(256) void k_map_columns(const double* __restrict__ 
 
 static const int kLdsBudget = 64 * 1024;      // bytes per workgroup
 
-// What the launch planning needs to know about the device (queried once per process) and the tuning knobs of the
-// environment (read once, at the first launch - never on the launch path again).
+// What the launch planning needs to know about the device (queried once per process) and the options (csrc/ttm_options.h).
 struct DeviceInfo {
     int cus = 256;                 // compute units
     size_t lds_per_cu = 160 * 1024;   // bytes of LDS a workgroup may be granted (gfx950: 160 KB per CU)
@@ -2878,71 +2878,8 @@ static const DeviceInfo& device_info() {
     }();
     return di;
 }
-// Options: what a test or a tuning run may override (ttm_set_option).  The defaults come from the environment
-// (TTM_<NAME IN UPPER CASE>), which is read ONCE, when the library is first used - never on the launch path.
-// -1 = "let the launch planning decide".
-#define TTM_OPTIONS(X)                                                                                                   \
-    X(no_plan, 0)        /* 1: generic kernels instead of the planned-cache ones                                     */ \
-    X(no_uform, 0)       /* 1: direct kernels instead of the U-form ones                                             */ \
-    X(u_no_hot, 0)       /* 1: U-form kernels without hot records                                                    */ \
-    X(u_loader, -1)      /* 0 / 1: loader-wave forward kernels off / on whatever the ensemble size                   */ \
-    X(forward_ns, -1)    /* samples per thread of the generic forward kernels (1, 2, 4)                              */ \
-    X(inverse_ns, -1)    /* samples per thread of the generic table inverse (1, 2)                                   */ \
-    X(u_ns, -1)          /* samples per thread of k_forward_u (1, 2, 4)                                              */ \
-    X(hl_ns, -1)         /* samples per evaluating thread of k_forward_hl (2, 4)                                     */ \
-    X(u_xlead, -1)       /* ring depths of the loader-wave forward kernels                                           */ \
-    X(u_tlead, -1)                                                                                                       \
-    X(u_wgs, -1)         /* workgroups per CU of the U-form forward kernels                                          */ \
-    X(rt_off, 0)         /* 1: table inverse through the generic kernel instead of k_inverse_rt                      */ \
-    X(rt_threads, -1)    /* threads per workgroup of k_inverse_rt (multiple of 64, <= 1024)                          */ \
-    X(rt_ns, -1)         /* rows per thread of k_inverse_rt (2, 4)                                                   */ \
-    X(rt_block, -1)      /* components per block of k_inverse_rt                                                     */ \
-    X(rt_etab, -1)       /* 0: exp(-x^2/4) of the put from the series instead of the interval table                  */ \
-    X(rt_band, -1)       /* 0: banded maps through the LDS column cache instead of the register shift                */ \
-    X(rt_window, -1)     /* resident entries per table of k_inverse_rt: 0 whole tables, > 0 that many, -1 planned    */ \
-    X(gram_mfma, -1)     /* 0: Gram matrices by the pairwise kernel instead of the matrix cores                      */ \
-    X(band_fwd, -1)      /* 0: banded maps through k_forward_hl instead of the push-form kernel (csrc/ttm_band.hip)   */ \
-    X(band_inv, -1)      /* 0: banded maps through k_inverse_rt instead of the push-form kernel                      */ \
-    X(band_cus, -1)      /* > 0: the band kernels plan their row chunks for this many CUs (tests: several tiles per chunk) */ \
-    X(band_ring, -1)     /* 0: banded table inverse through k_band_inverse (tables assembled per block) although images are at hand */ \
-    X(int_dense, -1)     /* 0: integrated maps with dense B sets through the generic kernels instead of csrc/ttm_int.hip */ \
-    X(int_xprog, -1)     /* 0: integrated components without their X programs (csrc/ttm_xprog.h: forward map, objective / gradient sums); \
-                            2: the root searches through them as well (measured: the weights are 1 % of a bisection - no gain, 5 % slower at C2a) */ \
-    X(int_wgs, -1)       /* > 0: workgroups per CU of the dense integrated kernels (default: one workgroup per tile of samples) */ \
-    X(int_chunks, -1)    /* > 0: component chunks of the dense integrated forward kernel (default: planned from the ensemble size) */ \
-    X(fold_fused, -1)    /* 0: ttm_fold as three launches (k_fold, k_uform, k_band_records) instead of one                */ \
-    X(table_fused, -1)   /* 0: inverse tables as two launches (k_table_build, k_table_index) instead of one               */ \
-    X(setup_fused, -1)   /* 0: ttm_setup_staged declines (the caller then launches ttm_fold_staged and the table kernel)           */ \
-    X(select_coop, -1)   /* 0: order statistics by 17 launches (k_select_hist / k_select_pick) whatever the column length;         \
-                            2: tests - the one-launch select with every wait given up at once (workgroup 0 selects by itself)    */ \
-    X(colstats_one, -1)  /* 0: column moments by four launches (k_colsum / k_colfinish) whatever the shape                        */ \
-    X(sep_sentinel, -1)  /* 0: the evaluations of ttm_optimize_separable with ticket and completion mark whatever the grid;       \
-                            2: tests - the finishing workgroup gives up at once (the failure pattern reaches the host)            */ \
-    X(sep_server, -1)    /* 0: the loops of ttm_optimize_separable launch per evaluation instead of ONE evaluation server per loop      */ \
-    X(roundtrip_fused, -1) /* 0: ttm_roundtrip declines (the caller makes the forward and the inverse call); 1: the fused kernel for \
-                              every shape it can run, also those it is slower for (reach of three columns, density terms)          */
-struct Tuning {
-#define X(name, dflt) int name = dflt;
-    TTM_OPTIONS(X)
-#undef X
-};
-static Tuning tuning_from_env() {
-    Tuning u;
-    auto geti = [](const char* name, int dflt) {
-        char env[64] = "TTM_";
-        size_t n = 4;
-        for (const char* c = name; *c && n < sizeof(env) - 1; ++c) env[n++] = (char)((*c >= 'a' && *c <= 'z') ? *c - 32 : *c);
-        env[n] = 0;
-        const char* e = getenv(env);
-        return e ? atoi(e) : dflt;
-    };
-#define X(name, dflt) u.name = geti(#name, dflt);
-    TTM_OPTIONS(X)
-#undef X
-    return u;
-}
 static Tuning& tuning() {
-    static Tuning t = tuning_from_env();
+    static Tuning t;
     return t;
 }
 
@@ -2960,13 +2897,26 @@ static int grid_for(int64_t N, int per_block) {
 // (the forward map's tile is short - one evaluation per sample: six workgroups per CU walking the tiles take 6 % less than one
 // workgroup per tile at C2a, whose 7 814 workgroups each pay their launch and their first load; nothing at C5-int.  The root
 // searches keep one workgroup per tile.)
-static int int_grid_for(int64_t N, int per_block, int default_wgs = 0) {
+static int int_grid_for(int64_t N, int per_block, int wgs = 0) {
     int64_t tiles = (N + per_block - 1) / per_block;
-    const int wgs = tuning().int_wgs > 0 ? tuning().int_wgs : default_wgs;
     const int64_t cap = wgs > 0 ? (int64_t)device_info().cus * wgs : ((int64_t)1 << 20);
     if (tiles > cap) tiles = cap;
     if (tiles < 1) tiles = 1;
     return (int)tiles;
+}
+
+// persistent grid: the tiles, but at most `wgs` workgroups per CU
+static int64_t persistent_grid(int64_t tiles, int wgs) {
+    const int64_t cap = (int64_t)device_info().cus * wgs;
+    return tiles < cap ? tiles : cap;
+}
+
+// the CUs the band kernels plan their row chunks for (option band_cus: tests)
+static int band_cus() { return tuning().band_cus > 0 ? tuning().band_cus : device_info().cus; }
+
+// resident-table images of the components [k0, k1) for this table geometry (ttm_band::image_plan with the options' window and block)
+static bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, int* w0, int* W, int* slot) {
+    return ttm_band::image_plan(p, k0, k1, T, nb, device_info().lds_per_cu, tuning().rt_window, tuning().rt_block, w0, W, slot);
 }
 
 static DevProg dev_prog(const ttm_program* p) {
@@ -3006,11 +2956,13 @@ static size_t lds_bytes(int nslots, int bd, int extra_doubles, int ns = 1) {
     return ((size_t)TTM_ERF_TABLE_LEN + (size_t)(TTM_CACHE_SLOTS + nslots) * ns * bd + extra_doubles) * 8;
 }
 
+static int plan_ways_of(const ttm_program* p) {
+    return (p->plan_ways < 1 || p->plan_ways > TTM_PLAN_WAYS) ? TTM_PLAN_WAYS : p->plan_ways;
+}
+
 // LDS image of the planned-cache kernels: erf table + 2 slots per way
 static size_t lds_bytes_plan(const ttm_program* p, int bd, int ns) {
-    int ways = p->plan_ways;
-    if (ways < 1 || ways > TTM_PLAN_WAYS) ways = TTM_PLAN_WAYS;
-    return ((size_t)TTM_ERF_TABLE_LEN + (size_t)2 * ways * ns * bd) * 8;
+    return ((size_t)TTM_ERF_TABLE_LEN + (size_t)2 * plan_ways_of(p) * ns * bd) * 8;
 }
 
 // largest block size whose LDS image fits; 0 if none
@@ -3082,15 +3034,14 @@ const char* ttm_last_kernel(void) { return g_last_kernel; }
 
 int ttm_set_option(const char* name, int32_t value) {
     if (!name) return set_err(TTM_E_ARG, "ttm_set_option: null name%s");
-    Tuning& t = tuning();
-#define X(field, dflt) if (!strcmp(name, #field)) { t.field = (int)value; return TTM_OK; }
-    TTM_OPTIONS(X)
-#undef X
-    return set_err(TTM_E_ARG, "ttm_set_option: unknown option '%s'", name);
+    int* field = tuning_field(tuning(), name);
+    if (!field) return set_err(TTM_E_ARG, "ttm_set_option: unknown option '%s'", name);
+    *field = (int)value;
+    return TTM_OK;
 }
 
 int ttm_reset_options(void) {
-    tuning() = tuning_from_env();
+    tuning() = Tuning{};
     return TTM_OK;
 }
 
@@ -3222,12 +3173,46 @@ static void allow_big_lds(const void* kern, size_t bytes) {
     if (n < 64) { seen[n] = kern; granted[n] = bytes; ++n; }
 }
 
-static int plan_ways_of(const ttm_program* p) {
-    return (p->plan_ways < 1 || p->plan_ways > TTM_PLAN_WAYS) ? TTM_PLAN_WAYS : p->plan_ways;
-}
-
 static bool u_on(const ttm_program* p) {
     return p->u_enabled && p->ucomp && p->ugrp && p->umono && p->ugeo && p->h_ucomp && p->h_ugrp && !tuning().no_uform;
+}
+
+// Horner degrees of the nonmonotone groups of [k0, k1) -> the smallest fixed-degree instantiation (0: 3/1, 1: 5/5, 2: 7/7, 3: 10/10)
+static int horner_class(const ttm_program* p, int k0, int k1) {
+    int mb = 0, ma = 0;
+    for (int k = k0; k < k1; ++k) {
+        const int* uc = p->h_ucomp + k * TTM_UC_LEN;
+        for (int g = 0; g < uc[TTM_UC_N_GRP]; ++g) {
+            const int fl = p->h_ugrp[(uc[TTM_UC_GRP_OFF] + g) * TTM_UG_LEN + TTM_UG_FLAGS];
+            if ((fl & TTM_PLAN_HF) && TTM_UG_DEGB(fl) > mb) mb = TTM_UG_DEGB(fl);
+            if ((fl & TTM_UGF_POLY) && TTM_UG_DEGA(fl) > ma) ma = TTM_UG_DEGA(fl);
+        }
+    }
+    return (mb <= 3 && ma <= 1) ? 0 : ((mb <= 5 && ma <= 5) ? 1 : ((mb <= 7 && ma <= 7) ? 2 : 3));
+}
+
+// Does ttm_forward take the band kernels (csrc/ttm_band.hip) for [k0, k1) of this map at N samples?  Shape and options only;
+// ttm_band::forward may still decline for the buffers it is given.
+static bool band_forward_gate(const ttm_program* p, int k0, int k1, int64_t N) {
+    const Tuning& tn = tuning();
+    return p->monotonicity == TTM_MONO_SEPARABLE && u_on(p) && all_fast(p, k0, k1) && N < ((int64_t)1 << 29) && tn.band_fwd != 0 &&
+           !tn.u_no_hot && (N >= 64 * 1024 || tn.band_fwd == 1) && ttm_band::usable(p, k0, k1);
+}
+
+// Does ttm_inverse_table take the resident-table kernels (k_inverse_rt, and the band kernels where band_inverse_gate holds)
+// for [k0, k1) at N samples and this table geometry?  Shape and options only: the caller checks that the tables come with an
+// affine abscissa (h_y_affine, ldy = 0).  (Small ensembles: the table load per workgroup does not pay; option u_loader = 1
+// forces it.)
+static bool rt_inverse_gate(const ttm_program* p, int k0, int k1, int64_t N, int T, int nb) {
+    const Tuning& tn = tuning();
+    return p->monotonicity == TTM_MONO_SEPARABLE && u_on(p) && p->u_h_cls >= 1 && p->u_h_cls <= 4 &&
+           (p->u_h_ng == 2 || p->u_h_ng == 4 || p->u_p_lag > 2) && all_fast(p, k0, k1) && T <= 4096 && nb <= 65535 && N < ((int64_t)1 << 28) &&
+           !tn.rt_off && !tn.u_no_hot && (N >= 64 * 1024 || tn.u_loader == 1);
+}
+
+// ... and the band kernels among them (csrc/ttm_band.hip; clipped searches only, which the caller checks)
+static bool band_inverse_gate(const ttm_program* p, int k0, int k1, int64_t N, int T, int nb) {
+    return rt_inverse_gate(p, k0, k1, N, T, nb) && tuning().band_inv != 0 && ttm_band::usable(p, k0, k1);
 }
 
 int64_t ttm_fold_size(const ttm_program* p) {
@@ -3309,7 +3294,6 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
         // a small ensemble is split over the components as well, until the launch has ~16 workgroups per CU to balance with
         const int tiles = ibd ? int_grid_for(N, ibd, 6) : 1;
         int nchunk = (int)(((int64_t)device_info().cus * 16 + tiles - 1) / tiles);
-        if (tuning().int_chunks > 0) nchunk = tuning().int_chunks;
         if (nchunk > k1 - k0) nchunk = k1 - k0;
         if (nchunk < 1) nchunk = 1;
         const int chunk = (k1 - k0 + nchunk - 1) / nchunk;
@@ -3324,14 +3308,12 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
             const int c = TTM_U_TSTRIDE * p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI];
             tab_cap = c > tab_cap ? c : tab_cap;
         }
-        int ways = p->plan_ways;
-        if (ways < 1 || ways > TTM_PLAN_WAYS) ways = TTM_PLAN_WAYS;
+        const int ways = plan_ways_of(p);
         // banded maps, large ensembles: push-form kernel with every spline resident in LDS (csrc/ttm_band.hip)
-        if (tuning().band_fwd != 0 && !tuning().u_no_hot && (N >= 64 * 1024 || tuning().band_fwd == 1) && ttm_band::usable(p, k0, k1)) {
+        if (band_forward_gate(p, k0, k1, N)) {
             const char* name = nullptr;
-            if (ttm_band::forward(p, fold + fold_base_size(p), k0, k1, Xsoa, ldx, N, Zsoa, ldz, logdet, sigma, sumsq,
-                                  tuning().band_cus > 0 ? tuning().band_cus : device_info().cus, device_info().lds_per_cu, tuning().rt_block,
-                                  stream, &name) == 0)
+            if (ttm_band::forward(p, fold + fold_base_size(p), k0, k1, Xsoa, ldx, N, Zsoa, ldz, logdet, sigma, sumsq, band_cus(),
+                                  device_info().lds_per_cu, tuning().rt_block, stream, &name) == 0)
                 return check_launch(name);
         }
         // large ensembles with aligned columns: loader-wave kernel
@@ -3345,10 +3327,6 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
             const int tab_slot = TTM_U_TSTRIDE * nimax;                   // doubles (nI is even: 16-byte multiple)
             int xlead = 3, tlead = 2;
             const Tuning& tn = tuning();
-            if (tn.u_xlead > 0) xlead = tn.u_xlead;
-            if (tn.u_tlead > 0) tlead = tn.u_tlead;
-            xlead = xlead < 1 ? 1 : (xlead > 4 ? 4 : xlead);
-            tlead = tlead < 1 ? 1 : (tlead > 2 ? 2 : tlead);
             // samples per evaluating thread of the hot kernels: four (a wave issues at most one fp64 instruction every
             // ~8 cycles and a dependent one only after ~30, tools/micro/fp64_peak.hip: the Horner chains of four
             // samples interleave to that rate; with two the chains wait on themselves)
@@ -3359,7 +3337,7 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
             const int hcw = TTM_HL_FWD_CW(logdet != nullptr);            // evaluating waves per workgroup of the hot kernel
             const int rows = hot ? hcw * 64 * hNS : TTM_UL_ROWS;
             auto lds_for = [&](int xl, int tl) { return ((size_t)(xl + 1) * rows + (size_t)(tl + 1) * tab_slot + (size_t)2 * ways * rows + TTM_EXPQ_TABLE_LEN) * 8; };
-            if (hot && tn.u_xlead <= 0 && tn.u_tlead <= 0) {
+            if (hot) {
                 // shallower rings when they buy a workgroup per CU (more independent phases per CU outweigh the look-ahead:
                 // 0.155 -> 0.152 ms at C5 with five workgroups and one-step rings)
                 static const int cand[4][2] = {{3, 2}, {2, 2}, {2, 1}, {1, 1}};
@@ -3393,9 +3371,7 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
                 int wgs = (int)(device_info().lds_per_cu / lds_ul);
                 if (wgs > 32 / (hcw + 2)) wgs = 32 / (hcw + 2);
                 if (wgs < 1) wgs = 1;
-                if (tn.u_wgs > 0) wgs = tn.u_wgs;
-                const int64_t tiles = (N + rows - 1) / rows;
-                const int64_t grid = tiles < (int64_t)device_info().cus * wgs ? tiles : (int64_t)device_info().cus * wgs;
+                const int64_t grid = persistent_grid((N + rows - 1) / rows, wgs);
                 allow_big_lds((const void*)hk, lds_ul);
                 hipLaunchKernelGGL(hk, dim3((unsigned)grid), dim3((hcw + 2) * 64), lds_ul, (hipStream_t)stream, p->ucomp,
                                    fold + fold_base_size(p), (int64_t)p->u_h_off, (int)p->D, (int)k0, (int)k1, Xsoa, ldx, N, Zsoa, ldz,
@@ -3405,24 +3381,13 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
             if (use_ul && !hot) {
                 typedef void (*lkern_t)(const int*, const int*, const double*, int, int, int, const double*, int64_t, int64_t,
                                         double*, int64_t, double*, const double*, double*, int, int, int);
-                int mb = 0, ma = 0;
-                for (int k = k0; k < k1; ++k) {
-                    const int* uc = p->h_ucomp + k * TTM_UC_LEN;
-                    for (int g = 0; g < uc[TTM_UC_N_GRP]; ++g) {
-                        const int fl = p->h_ugrp[(uc[TTM_UC_GRP_OFF] + g) * TTM_UG_LEN + TTM_UG_FLAGS];
-                        if ((fl & TTM_PLAN_HF) && TTM_UG_DEGB(fl) > mb) mb = TTM_UG_DEGB(fl);
-                        if ((fl & TTM_UGF_POLY) && TTM_UG_DEGA(fl) > ma) ma = TTM_UG_DEGA(fl);
-                    }
-                }
-                const int cls = (mb <= 3 && ma <= 1) ? 0 : ((mb <= 5 && ma <= 5) ? 1 : ((mb <= 7 && ma <= 7) ? 2 : 3));
+                const int cls = horner_class(p, k0, k1);
                 lkern_t lk = logdet ? (cls == 0 ? k_forward_ul<true, 3, 1> : cls == 1 ? k_forward_ul<true, 5, 5> : cls == 2 ? k_forward_ul<true, 7, 7> : k_forward_ul<true, 10, 10>)
                                     : (cls == 0 ? k_forward_ul<false, 3, 1> : cls == 1 ? k_forward_ul<false, 5, 5> : cls == 2 ? k_forward_ul<false, 7, 7> : k_forward_ul<false, 10, 10>);
                 int wgs = (int)(device_info().lds_per_cu / lds_ul);
                 if (wgs > 32 / (TTM_UL_CW + 2)) wgs = 32 / (TTM_UL_CW + 2);                                    // 6 waves per workgroup, 32 per CU
                 if (wgs < 1) wgs = 1;
-                if (tn.u_wgs > 0) wgs = tn.u_wgs;
-                const int64_t tiles = (N + TTM_UL_ROWS - 1) / TTM_UL_ROWS;
-                const int64_t grid = tiles < (int64_t)device_info().cus * wgs ? tiles : (int64_t)device_info().cus * wgs;
+                const int64_t grid = persistent_grid((N + TTM_UL_ROWS - 1) / TTM_UL_ROWS, wgs);
                 allow_big_lds((const void*)lk, lds_ul);
                 hipLaunchKernelGGL(lk, dim3((unsigned)grid), dim3(TTM_UL_THREADS), lds_ul, (hipStream_t)stream, p->ucomp, p->ugrp,
                                    fold + fold_base_size(p), (int)p->D, (int)k0, (int)k1, Xsoa, ldx, N, Zsoa, ldz, logdet, sigma, sumsq,
@@ -3438,17 +3403,7 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
         if (lds <= (size_t)kLdsBudget) {
             typedef void (*ukern_t)(const int*, const int*, const double*, int, int, int, const double*, int64_t, int64_t, double*,
                                     int64_t, double*, const double*, double*, int);
-            // Horner degrees of the nonmonotone groups in this launch -> smallest fixed-degree instantiation
-            int mb = 0, ma = 0;
-            for (int k = k0; k < k1; ++k) {
-                const int* uc = p->h_ucomp + k * TTM_UC_LEN;
-                for (int g = 0; g < uc[TTM_UC_N_GRP]; ++g) {
-                    const int fl = p->h_ugrp[(uc[TTM_UC_GRP_OFF] + g) * TTM_UG_LEN + TTM_UG_FLAGS];
-                    if ((fl & TTM_PLAN_HF) && TTM_UG_DEGB(fl) > mb) mb = TTM_UG_DEGB(fl);
-                    if ((fl & TTM_UGF_POLY) && TTM_UG_DEGA(fl) > ma) ma = TTM_UG_DEGA(fl);
-                }
-            }
-            const int cls = (mb <= 3 && ma <= 1) ? 0 : ((mb <= 5 && ma <= 5) ? 1 : ((mb <= 7 && ma <= 7) ? 2 : 3));
+            const int cls = horner_class(p, k0, k1);
 #define TTM_UK(L, NSV) (cls == 0 ? k_forward_u<L, NSV, 3, 1> : cls == 1 ? k_forward_u<L, NSV, 5, 5> : cls == 2 ? k_forward_u<L, NSV, 7, 7> : k_forward_u<L, NSV, 10, 10>)
             ukern_t uk = logdet ? (uNS == 4 ? TTM_UK(true, 4) : uNS == 2 ? TTM_UK(true, 2) : TTM_UK(true, 1))
                                 : (uNS == 4 ? TTM_UK(false, 4) : uNS == 2 ? TTM_UK(false, 2) : TTM_UK(false, 1));
@@ -3456,9 +3411,7 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
             int wgs_per_cu = (int)(device_info().lds_per_cu / (lds ? lds : 1));
             if (wgs_per_cu > 8) wgs_per_cu = 8;
             if (wgs_per_cu < 1) wgs_per_cu = 1;
-            if (tuning().u_wgs > 0) wgs_per_cu = tuning().u_wgs;
-            int64_t tiles = (N + (int64_t)uNS * ubd - 1) / ((int64_t)uNS * ubd);
-            int64_t grid = tiles < (int64_t)device_info().cus * wgs_per_cu ? tiles : (int64_t)device_info().cus * wgs_per_cu;
+            const int64_t grid = persistent_grid((N + (int64_t)uNS * ubd - 1) / ((int64_t)uNS * ubd), wgs_per_cu);
             hipLaunchKernelGGL(uk, dim3((unsigned)grid), dim3(ubd), lds, (hipStream_t)stream, p->ucomp, p->ugrp,
                                fold + fold_base_size(p), (int)p->D, (int)k0, (int)k1, Xsoa, ldx, N, Zsoa, ldz, logdet, sigma, sumsq, tab_cap);
             return check_launch("k_forward_u");
@@ -3531,9 +3484,7 @@ int ttm_inverse_table_index(const double* tab_x, int32_t ncomp, int32_t T, int32
 int64_t ttm_inverse_table_image_doubles(const ttm_program* p, int32_t k0, int32_t k1, int32_t T, int32_t nb) {
     if (validate(p, k0, k1) || T < 2 || T > 2048 || nb + 1 != 1024 || !u_on(p) || tuning().band_inv == 0) return 0;
     int w0, W, slot;
-    const Tuning& tn = tuning();
-    if (!ttm_band::image_plan(p, k0, k1, (int)T, (int)nb, device_info().lds_per_cu, tn.rt_window, tn.rt_block, &w0, &W, &slot)) return 0;
-    return slot;
+    return image_plan(p, k0, k1, (int)T, (int)nb, &w0, &W, &slot) ? slot : 0;
 }
 
 int ttm_inverse_table_build_index(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1, const double* pts,
@@ -3546,9 +3497,7 @@ int ttm_inverse_table_build_index(const ttm_program* p, const double* coef, cons
     if (p->monotonicity != TTM_MONO_SEPARABLE) return set_err(TTM_E_UNSUPPORTED, "table inverse needs separable monotonicity%s");
     int iw0 = 0, iW = 0, islot = 0;
     if (img) {
-        const Tuning& tn = tuning();
-        if ((uintptr_t)img % 16 != 0 || ttm_inverse_table_image_doubles(p, k0, k1, T, nb) == 0 ||
-            !ttm_band::image_plan(p, k0, k1, (int)T, (int)nb, device_info().lds_per_cu, tn.rt_window, tn.rt_block, &iw0, &iW, &islot))
+        if ((uintptr_t)img % 16 != 0 || ttm_inverse_table_image_doubles(p, k0, k1, T, nb) == 0 || !image_plan(p, k0, k1, (int)T, (int)nb, &iw0, &iW, &islot))
             return set_err(TTM_E_ARG, "ttm_inverse_table_build_index: no resident-table images for this map and table geometry "
                                       "(ttm_inverse_table_image_doubles returns 0)%s");
     }
@@ -3593,7 +3542,7 @@ int ttm_setup_staged(const ttm_program* p, const double* h_coef, double* coef, d
     int iw0 = 0, iW = 0, islot = 0;
     if (img) {
         if ((uintptr_t)img % 16 != 0 || ttm_inverse_table_image_doubles(p, 0, p->D, T, nb) == 0 ||
-            !ttm_band::image_plan(p, 0, p->D, (int)T, (int)nb, device_info().lds_per_cu, tn.rt_window, tn.rt_block, &iw0, &iW, &islot))
+            !image_plan(p, 0, p->D, (int)T, (int)nb, &iw0, &iW, &islot))
             return set_err(TTM_E_ARG, "ttm_setup_staged: no resident-table images for this map and table geometry%s");
     }
     const int ns = map_slots(p, 0, p->D);
@@ -3623,17 +3572,11 @@ int ttm_roundtrip(const ttm_program* p, const double* coef, const double* fold, 
     if (!coef || !fold || !Xsoa || !Xr || !tab_x || !tmin || !tmax || !bkt || !h_y_affine || N < 1 || ldx < N || ldr < N || (Zsoa && ldz < N) ||
         T < 8 || T > 65536 || nb < 4 || nb > 65536)
         return set_err(TTM_E_ARG, "ttm_roundtrip: bad arguments%s");
-    // the conditions of the two calls it stands for (ttm_forward -> k_band_few, ttm_inverse_table -> k_band_few_inverse)
-    const Tuning& tn = tuning();
-    if (p->monotonicity != TTM_MONO_SEPARABLE || !u_on(p) || p->u_h_cls < 1 || p->u_h_cls > 4 || !all_fast(p, 0, p->D) || tn.rt_off || tn.u_no_hot ||
-        tn.band_fwd == 0 || tn.band_inv == 0 || tn.roundtrip_fused == 0 || !(N >= 64 * 1024 || (tn.band_fwd == 1 && tn.u_loader == 1)) ||
-        !ttm_band::usable(p, 0, p->D))
-        return TTM_E_UNSUPPORTED;
-    const DeviceInfo& di = device_info();
+    // only where the two calls it stands for take the band kernels (ttm_forward -> k_band_few, ttm_inverse_table -> k_band_few_inverse)
+    if (!band_forward_gate(p, 0, p->D, N) || !band_inverse_gate(p, 0, p->D, N, T, nb) || tuning().roundtrip_fused == 0) return TTM_E_UNSUPPORTED;
     const char* name = nullptr;
     if (ttm_band::roundtrip(p, fold + fold_base_size(p), 0, p->D, Xsoa, ldx, N, Zsoa, ldz, Xr, ldr, logdet, sigma, sumsq, tab_x, (int)T, h_y_affine,
-                            tmin, tmax, bkt, (int)nb, tn.band_cus > 0 ? tn.band_cus : di.cus, di.lds_per_cu, tn.roundtrip_fused == 1, stream,
-                            &name) != 0)
+                            tmin, tmax, bkt, (int)nb, band_cus(), device_info().lds_per_cu, tuning().roundtrip_fused == 1, stream, &name) != 0)
         return TTM_E_UNSUPPORTED;
     return check_launch(name);
 }
@@ -3648,23 +3591,21 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
         T < 8 || T > 65536 || nb < 4 || nb > 65536 || (ldy != 0 && ldy < T) || (h_y_affine && ldy != 0))
         return set_err(TTM_E_ARG, "ttm_inverse_table: bad arguments%s");
     if (p->monotonicity != TTM_MONO_SEPARABLE) return set_err(TTM_E_UNSUPPORTED, "table inverse needs separable monotonicity%s");
-    // large ensembles of maps with hot records: resident-table kernel (components in blocks, tables resident in LDS)
-    if (u_on(p) && p->u_h_cls >= 1 && p->u_h_cls <= 4 && (p->u_h_ng == 2 || p->u_h_ng == 4 || p->u_p_lag > 2) && all_fast(p, k0, k1) &&
-        h_y_affine && ldy == 0 && T <= 4096 && nb <= 65535 && N < ((int64_t)1 << 28) && !tuning().rt_off && !tuning().u_no_hot &&
-        (N >= 64 * 1024 || tuning().u_loader == 1)) {                       // (small ensembles: the table load per workgroup does not pay;
-                                                                            // option u_loader = 1 forces it)
+    // large ensembles of maps with hot records: resident-table kernels (components in blocks, tables resident in LDS)
+    const Tuning& tn = tuning();
+    const bool affine = h_y_affine && ldy == 0;
+    // banded maps: push-form kernel (csrc/ttm_band.hip); clipped searches only (exp(-x^2/4) from the located interval)
+    if (affine && truncate && band_inverse_gate(p, k0, k1, N, T, nb)) {
+        const char* name = nullptr;
+        if (ttm_band::inverse(p, fold + fold_base_size(p), k0, k1, Zsoa, ldz, Xsoa, ldx, N, tab_x, (int)T, h_y_affine, tmin, tmax, bkt, (int)nb,
+                              tn.band_ring != 0 ? img : nullptr, (int)img_doubles, band_cus(), device_info().lds_per_cu, tn.rt_window, tn.rt_block,
+                              stream, &name) == 0)
+            return check_launch(name);
+    }
+    // k_inverse_rt sweeps the hot records themselves: not for lag-3 maps (include/ttm.h), and with fewer than four
+    // components its table load per workgroup does not pay (order class 4: the few-component kernels only)
+    if (affine && rt_inverse_gate(p, k0, k1, N, T, nb) && p->u_p_lag <= 2 && p->u_h_cls <= 3 && (k1 - k0 >= 4 || tn.u_loader == 1)) {
         const DeviceInfo& di = device_info();
-        const Tuning& tn = tuning();
-        // banded maps: push-form kernel (csrc/ttm_band.hip); clipped searches only (exp(-x^2/4) from the located interval)
-        if (tn.band_inv != 0 && truncate && ttm_band::usable(p, k0, k1)) {
-            const char* name = nullptr;
-            if (ttm_band::inverse(p, fold + fold_base_size(p), k0, k1, Zsoa, ldz, Xsoa, ldx, N, tab_x, (int)T, h_y_affine, tmin, tmax, bkt, (int)nb,
-                                  tn.band_ring != 0 ? img : nullptr, (int)img_doubles, tn.band_cus > 0 ? tn.band_cus : di.cus, di.lds_per_cu, tn.rt_window, tn.rt_block, stream, &name) == 0)
-                return check_launch(name);
-        }
-      // k_inverse_rt sweeps the hot records themselves: not for lag-3 maps (include/ttm.h), and with fewer than four
-      // components its table load per workgroup does not pay
-      if (p->u_p_lag <= 2 && p->u_h_cls <= 3 && (k1 - k0 >= 4 || tn.u_loader == 1)) {      // (order class 4: the few-component kernels only)
         const int ways = plan_ways_of(p);
         const int ncomp = k1 - k0;
         int NS = tn.rt_ns == 4 ? 4 : 2;
@@ -3672,8 +3613,7 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
         int Weven = (W + 4 + 1) & ~1;
         int tab_slot = TTM_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1);   // doubles: header + xs window + uint16 bucket index (even)
         const double ymax = fabs(h_y_affine[0]) > fabs(h_y_affine[2]) ? fabs(h_y_affine[0]) : fabs(h_y_affine[2]);
-        bool etab = truncate && h_y_affine[1] > 0.0 && h_y_affine[1] * ymax * 0.5 <= 0.1;
-        if (tn.rt_etab == 0) etab = false;
+        const bool etab = truncate && h_y_affine[1] > 0.0 && h_y_affine[1] * ymax * 0.5 <= 0.1;
         const bool aligned = ((uintptr_t)Zsoa % 16 == 0) && (ldz % 2 == 0) && ldz >= ((N + 1) & ~(int64_t)1) &&
                              ((uintptr_t)Xsoa % 16 == 0) && (ldx % 2 == 0) && ldx >= ((N + 1) & ~(int64_t)1);
         // banded map: every nonmonotone group of component k reads column kc-1 or kc-2, columns consecutive -> the last
@@ -3693,7 +3633,7 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
         // per thread are 0.7 % faster, but a tile that re-reads its columns at a block boundary takes exp(-x^2/4) from the
         // series there instead of the interval: the last bits then depend on where the boundaries fall, i.e. on the window)
         if (band && tn.rt_ns <= 0 && (N + di.cus - 1) / di.cus <= 4 * 1024) NS = 4;
-        int CT = tn.rt_threads >= 64 && tn.rt_threads <= 1024 ? (tn.rt_threads & ~63) : 1024;
+        int CT = 1024;
         const size_t budget = di.lds_per_cu / wgs;
         int Bc = 0, nblk = 0;
         size_t lds = 0;
@@ -3757,7 +3697,6 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
                                h_y_affine[1], h_y_affine[2], tmin, tmax, bkt, (int)nb, (int)truncate, tab_slot, Bc, ways, rows, w0, W);
             return check_launch(band ? "k_inverse_rt<band>" : "k_inverse_rt");
         }
-      }
     }
     const int bd = 256;
     int NS = N >= 4 * 256 * 256 ? 2 : 1;       // two samples per thread for large ensembles (scalar work halves)

@@ -1001,8 +1001,7 @@ def uform_geometry(cm, kappa=None):
         cm.u_enabled = False
         return False
     if kappa is None:
-        import os
-        kappa = float(os.environ.get('TTM_U_KAPPA', U_KAPPA))      # (tuning knob)
+        kappa = U_KAPPA
     uc = cm.ucomp[:cm.D * UC_LEN].reshape(-1, UC_LEN)       # (view: the entry-state words follow)
     off, ok = 0, True
     geo = np.zeros((cm.D, 2))

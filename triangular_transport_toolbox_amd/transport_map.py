@@ -1111,12 +1111,8 @@ class transport_map():
         return self._empty((k1 - k0) * per) if per > 0 else None
 
     def _inv_nb(self):
-        """Buckets of the table index (~ table points; nb + 1 int32 per row = whole 16-byte units); TTM_INV_NB is read once."""
-        nb = getattr(transport_map, '_INV_NB', None)
-        if nb is None:
-            import os
-            nb = transport_map._INV_NB = int(os.environ.get('TTM_INV_NB', 1023))
-        return nb
+        """Buckets of the table index (~ table points; nb + 1 int32 per row = whole 16-byte units)."""
+        return 1023
 
     def _ensure_pts(self, resolution, start_distance):
         key = (resolution, start_distance)
