@@ -10,25 +10,29 @@ for integrated-rectifier maps).  value = N * D * steps / time, summed over ranks
 (weak scaling: every rank owns its own N-sample ensemble; the path has no
 data-path collective).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C5|C2a|C2b|C3] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C5|C2a|C2b|C3] [--dump-outputs DIR] [--full]
 
 `--dump-outputs DIR` writes what the last of the K timed steps computed - the forward map Z and the inverse X (in the
 standardised coordinates the device path works in), float64, one row per sample - at a fixed seeded sample of the
 ensemble (all of it when small) to DIR/forward_Z.npy and DIR/inverse_X.npy: the inputs are seeded, so two builds
 compare output for output.
 
-prints ONE JSON line (rank 0) with the `roofline` object of the dominant kernel - whichever of the two map
-kernels has the longer measured launch (today the table inverse; algorithmic bytes 8 N (d_used + D) forward,
-8 N (2 D + E) inverse) - the fractions of the other kernel and of the pair, an `fp64` block
-(arithmetic rate next to the byte rate) and a `cpu_baseline` object (rank 0, N=1).
+prints ONE JSON line (rank 0).  A plain run does only what the headline needs - set-up, pre-warm, the W warm-up and the
+K timed steps, the dump - and its line carries the headline (`value`, `ms_per_step`, ...), the configuration and how the
+steps were run.  `--full` also measures and checks everything else around the same timed steps, and its line adds:
+the `roofline` object of the dominant kernel - whichever of the two map kernels has the longer measured launch (today
+the table inverse; algorithmic bytes 8 N (d_used + D) forward, 8 N (2 D + E) inverse) - the
+fractions of the other kernel and of the pair, an `fp64` block (arithmetic rate next to the byte rate, SURVEY.md
+section 8d), the cold and uncached steps, the host-boundary numbers, optimize() and a `cpu_baseline` object (rank 0, N=1).
 
 `--gpus N` with N > 1 and no launcher in the environment (WORLD_SIZE unset) starts the N ranks itself: N fresh
 child processes, one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, before this
 process has touched the GPU; rank 0's JSON line is relayed.  Under torchrun (WORLD_SIZE set) every process is a rank.
 The headline workload is C5 (BASELINE.json configs[4], the one north_star's target is quoted on; it fits one GPU);
-at N=1 the same line carries, under `other_configs`, the secondary numbers of the other single-GPU configurations
-(configs[1] = C2b / C2a spiral d=2 order 5 N=1e6 forward + inverse + pullback, configs[2] = C3 d=4 order 4 N=5e5 with
-optimize()).  Timing discipline (pre-warm, no pause before the timed steps): DESIGN.md section 6, "Clock state".
+with `--full` at N=1 the same line carries, under `other_configs`, the secondary numbers of the other single-GPU
+configurations (configs[1] = C2b / C2a spiral d=2 order 5 N=1e6 forward + inverse + pullback, configs[2] = C3 d=4
+order 4 N=5e5 with optimize()), and at N > 1 the node-level extras (multi_gpu_extras).  Timing discipline (pre-warm,
+no pause before the timed steps): DESIGN.md section 6, "Clock state".
 """
 import argparse
 import json
@@ -828,12 +832,16 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--prewarm-seconds', type=float, default=2.0,
                     help='untimed back-to-back steps before the warm-up, until the chip holds its clock under load '
-                         '(MI355X_MICROARCH.md, DVFS item 6: >= 2 s); 0 = none.  The same K steps timed WITHOUT it are '
-                         'reported as cold_ms_per_step')
+                         '(MI355X_MICROARCH.md, DVFS item 6: >= 2 s); 0 = none.  With --full the same K steps timed '
+                         'WITHOUT it are reported as cold_ms_per_step')
     ap.add_argument('--workload', default='C5', choices=sorted(WORKLOADS))
     ap.add_argument('--n', '--samples', dest='n', type=int, default=0, help='override the ensemble size (testing only)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help="torch.distributed backend for --gpus > 1 ('nccl' = RCCL; 'gloo' only to rehearse on one GPU)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline: per-kernel and roofline '
+                         'figures, cold and uncached steps, optimize(), the host boundary, the CPU baseline, the other '
+                         'configurations and, at N > 1, the node-level extras (the --no-* options below skip parts of it)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-optimize', action='store_true')
     ap.add_argument('--no-api', action='store_true', help='skip the host-boundary numbers (ctor_s, api_map_ms, ...)')
@@ -880,7 +888,7 @@ def main():
         except (OSError, ValueError, subprocess.TimeoutExpired):
             pass
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         # first, before anything touches the GPU (the NumPy leg forks a worker)
         cpu = cpu_baseline(args.workload, args.cpu_seconds)
     import torch
@@ -950,11 +958,12 @@ def main():
         sync()
         return time.perf_counter() - t0
 
-    # (a) the contract's W + K steps straight from the cold start (no pre-warm): cold_ms_per_step
     step()                                           # (builds the tables kept with `coef`; first-launch costs)
-    for _ in range(args.warmup):
-        step()
-    cold = timed(step, args.steps)
+    if args.full:
+        # (a) the contract's W + K steps straight from the cold start (no pre-warm): cold_ms_per_step
+        for _ in range(args.warmup):
+            step()
+        cold = timed(step, args.steps)
     # (b) After any idle gap of a millisecond or more (and from a cold start) the chip runs this workload 10-30 % slower
     # for the next ~50 launches (20 ms) before it holds its clock again (tools/ramp_probe.py).  For the headline the
     # card is first kept busy with the same steps, untimed, for --prewarm-seconds, the W warm-up steps follow
@@ -981,9 +990,63 @@ def main():
     elapsed = timed(step, args.steps)
     dumped = None
     if args.dump_outputs and rank == 0:
-        # gathered on the device now: the measurements below overwrite Z and Xinv; written to disk at the end
+        # gathered on the device now: the measurements of --full overwrite Z and Xinv; written to disk at the end
         idx = torch.from_numpy(dump_sample_index(N, D + d)).to(Z.device)
         dumped = {'forward_Z': Z.index_select(1, idx), 'inverse_X': Xinv.index_select(1, idx)}
+
+    def write_dump():
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, t in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), np.ascontiguousarray(t.cpu().numpy().T))
+
+    def over_ranks(elapsed, *others):
+        """every rank's own ms per timed step (a straggler shows here; None on one rank), then `elapsed` and `others`
+        (seconds) as their maximum over the ranks - the contract's time"""
+        if dist is None:
+            return None, (elapsed,) + others
+        mine = torch.tensor([1e3 * elapsed / args.steps], dtype=torch.float64, device='cuda')
+        every = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(every, mine)
+        t = torch.tensor((elapsed,) + others, dtype=torch.float64, device='cuda')
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return [float(v.item()) for v in every], tuple(float(v) for v in t.tolist())
+
+    def headline(elapsed, per_rank_ms):
+        """the line of a plain run: the timed steps, the configuration and how the steps were run"""
+        return {
+            'metric': 'map-evals/sec (forward+inverse, N samples x D comps)',
+            'value': world * N * D * args.steps / elapsed,
+            'unit': 'map-evals/s',
+            'n_gpus': world,
+            'steps': args.steps,
+            'warmup': args.warmup,
+            'ms_per_step': 1e3 * elapsed / args.steps,
+            'per_rank_ms_per_step': per_rank_ms,
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f64',
+            'data': 'synthetic',
+            'config': {'workload': args.workload + ': ' + WORKLOADS[args.workload][3],
+                       'N_per_gpu': N, 'D': D, 'columns': d, 'inverse': 'table' if separable else 'bisection',
+                       'layout': 'column-major resident in HBM', 'coefficients': 'reference-optimised (tests/golden)',
+                       'world_size': (dist.get_world_size() if dist is not None else 1),
+                       'backend': (('rccl' if args.backend == 'nccl' else args.backend) if dist is not None else None)},
+            'prewarm': {'seconds': args.prewarm_seconds, 'steps': prewarm_steps,
+                        'why': 'untimed steps before the warm-up so that the timed steps run at the clock the chip holds under '
+                               'sustained load (after an idle gap >= 1 ms the next ~50 launches run 10-30 % slower); '
+                               'cold_ms_per_step of --full is the same measurement without it'},
+        }
+
+    if not args.full:
+        per_rank_ms, (elapsed,) = over_ranks(elapsed)
+        write_dump()
+        if rank == 0:
+            emit(headline(elapsed, per_rank_ms), last=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # per-kernel timing with HIP events on the launch stream, directly behind the timed steps (same clock state)
     lib = tm._lib
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -1023,16 +1086,7 @@ def main():
     uncached_deferred = timed(step_uncached_deferred, n_unc)
     tm.validate(unc_prev[0])
     tm.deferred_checks = False
-    per_rank_ms = None
-    if dist is not None:
-        # every rank's own clock over the timed steps (a straggler shows here), then the contract's maximum over the ranks
-        mine = torch.tensor([1e3 * elapsed / args.steps], dtype=torch.float64, device='cuda')
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        per_rank_ms = [float(v.item()) for v in every]
-        t = torch.tensor([elapsed, cold, uncached], dtype=torch.float64, device='cuda')
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, cold, uncached = [float(v) for v in t.tolist()]
+    per_rank_ms, (elapsed, cold, uncached) = over_ranks(elapsed, cold, uncached)
     # what a plain elementwise pass achieves on the same buffers in the same alternating pattern (X -> Z, Z -> Xinv: the
     # bytes of a step with no arithmetic), directly behind the timed steps: the card's own streaming floor for this step
     floor_ms = None
@@ -1248,25 +1302,8 @@ def main():
                            'forward_frac': (gbps(fwd_bytes, rp['forward_avg_ms']) / HBM_PEAK_GBS if rp.get('forward_avg_ms') else None),
                            'inverse_frac': (gbps(inv_bytes, rp['inverse_avg_ms']) / HBM_PEAK_GBS if rp.get('inverse_avg_ms') else None),
                            'note': 'another run (another box) of the same command under the profiler; profiled dispatches run a few % slower'}
-        out = {
-            'metric': 'map-evals/sec (forward+inverse, N samples x D comps)',
-            'value': world * N * D * args.steps / elapsed,
-            'unit': 'map-evals/s',
-            'n_gpus': world,
-            'steps': args.steps,
-            'warmup': args.warmup,
-            'ms_per_step': ms_step,
-            'per_rank_ms_per_step': per_rank_ms,
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f64',
-            'data': 'synthetic',
-            'config': {'workload': args.workload + ': ' + WORKLOADS[args.workload][3],
-                       'N_per_gpu': N, 'D': D, 'columns': d, 'inverse': 'table' if separable else 'bisection',
-                       'layout': 'column-major resident in HBM', 'coefficients': 'reference-optimised (tests/golden)',
-                       'world_size': (dist.get_world_size() if dist is not None else 1),
-                       'backend': (('rccl' if args.backend == 'nccl' else args.backend) if dist is not None else None)},
+        out = headline(elapsed, per_rank_ms)
+        out.update({
             # the dominant kernel = the one with the longer measured launch
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': achieved / HBM_PEAK_GBS,
@@ -1315,11 +1352,7 @@ def main():
             'cached': 'folded coefficients, U-form section and inverse tables are functions of the coefficient vector '
                       'and are built once before the timed region; uncached_ms_per_step rebuilds them every step '
                       '(the reference rebuilds its table in every inverse_map, TM:4047-4058)',
-            'prewarm': {'seconds': args.prewarm_seconds, 'steps': prewarm_steps,
-                        'why': 'untimed steps before the warm-up so that the timed steps run at the clock the chip holds under '
-                               'sustained load (after an idle gap >= 1 ms the next ~50 launches run 10-30 % slower); '
-                               'cold_ms_per_step is the same measurement without it'},
-        }
+        })
         fl = fl_pre
         if fl is not None:
             tf = lambda f, ms: f * N * D / (ms * 1e-3) / 1e12          # noqa: E731
@@ -1332,10 +1365,7 @@ def main():
         out.update(extra)
         if cpu is not None:
             out['cpu_baseline'] = cpu
-    if dumped is not None:
-        os.makedirs(args.dump_outputs, exist_ok=True)
-        for name, t in dumped.items():
-            np.save(os.path.join(args.dump_outputs, name + '.npy'), np.ascontiguousarray(t.cpu().numpy().T))
+    write_dump()
     if world > 1:
         # The node-level extras (strong scaling, the sample-sharded filter, the component-partitioned optimize()) are the
         # first code of this repository that runs RCCL collectives of its own over more than one rank: they run behind the

@@ -43,11 +43,11 @@ def test_no_fork_after_gpu_initialisation_in_bench():
 
 @pytest.mark.gpu
 def test_two_rank_gloo_rehearsal_yields_one_json_line_with_the_node_level_keys():
-    """`bench.py --gpus 2 --backend gloo` on the one-GPU box: the never-GPU parent starts two ranks, rank 0's guardian
-    prints exactly one JSON line; its node-level keys are pinned here.  (What the guardian prints when rank 0 dies is
-    checked above without a GPU.)"""
+    """`bench.py --gpus 2 --backend gloo --full` on the one-GPU box: the never-GPU parent starts two ranks, rank 0's
+    guardian prints exactly one JSON line; its node-level keys are pinned here.  (What the guardian prints when rank 0
+    dies is checked above without a GPU.)"""
     res = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1',
-                          '--n', '70001', '--prewarm-seconds', '0', '--no-optimize', '--extras-timeout', '400'],
+                          '--n', '70001', '--prewarm-seconds', '0', '--no-optimize', '--extras-timeout', '400', '--full'],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout[-2000:] + res.stderr[-2000:]

@@ -6,7 +6,7 @@ mkdir -p "$out"
 i=0
 for cfg in "$@"; do
     i=$((i+1))
-    env $cfg python bench.py --no-cpu-baseline --no-optimize --no-other-configs --steps 100 > "$out/ab_$i.json" 2> "$out/ab_$i.err" || { echo "variant '$cfg' failed"; tail -5 "$out/ab_$i.err"; }
+    env $cfg python bench.py --full --no-cpu-baseline --no-optimize --no-other-configs --steps 100 > "$out/ab_$i.json" 2> "$out/ab_$i.err" || { echo "variant '$cfg' failed"; tail -5 "$out/ab_$i.err"; }
     python - "$out/ab_$i.json" "$cfg" <<'PY'
 import json, sys
 try:
