@@ -535,7 +535,10 @@ int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* f
  * dS/dx_k (midpoint when a step leaves the bracket).  Converges to the same root in ~6 instead of
  * ~33 evaluations of S; the last trial point is not the reference's last midpoint (difference
  * <= 1e-9 / (dS/dx)).  Opt-in of the host class (root_finder='newton'); the default stays
- * ttm_inverse_bisect.  iters: as above (maximum number of Newton / midpoint trial points).        */
+ * ttm_inverse_bisect.  iters: as above (maximum number of Newton / midpoint trial points).
+ * Banded separable maps with push records take the same search in push form under the size gate of
+ * the table inverse (k_band_newton / k_band_few_newton, csrc/ttm_band.hip: the monotone part is the
+ * component's resident spline; option band_newton = 0: the generic kernel).                       */
 int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1,
                        const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
                        int32_t* iters, void* stream);

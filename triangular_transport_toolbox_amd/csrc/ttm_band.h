@@ -41,6 +41,12 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
             int64_t N, const double* tab_x, int T, const double* y_affine, const double* tmin, const double* tmax, const int32_t* bkt,
             int nb, const double* img, int img_doubles, int cus, size_t lds_per_cu, int window, int block, void* stream, const char** kernel_name);
 
+// safeguarded Newton root search (sample_newton, csrc/ttm_eval.h: bracket +-2, window doubling, |S - z| <= 1e-9, at most 100
+// trial points) in push form: the monotone part is the component's resident spline (+ the linear own term of a map of a few
+// components), no tables.  Conditioning columns (if any) are read from Xsoa.  iters: as ttm_inverse_newton.  1: declined
+int newton(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
+           int32_t* iters, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name);
+
 // forward map (+ log-determinant / sum of squares) and the table inverse of the image, in ONE launch, for maps of a few components
 // (k_band_few_roundtrip): Z (nullable) = S(X), Xr = S^-1(S(X)) - conditioning columns are read from X.  Without `force` only the
 // shapes the one launch is faster for (reach <= 2 columns, no density terms); 1: declined

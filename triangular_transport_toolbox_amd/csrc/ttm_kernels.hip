@@ -3203,16 +3203,26 @@ static bool band_forward_gate(const ttm_program* p, int k0, int k1, int64_t N) {
 // for [k0, k1) at N samples and this table geometry?  Shape and options only: the caller checks that the tables come with an
 // affine abscissa (h_y_affine, ldy = 0).  (Small ensembles: the table load per workgroup does not pay; option u_loader = 1
 // forces it.)
-static bool rt_inverse_gate(const ttm_program* p, int k0, int k1, int64_t N, int T, int nb) {
+// (the size in it is transport_map.NEWTON_BAND_MIN_ROWS on the Python side: the pipelined Newton inverse sizes its chunks by it)
+static bool rt_shape_gate(const ttm_program* p, int k0, int k1, int64_t N) {
     const Tuning& tn = tuning();
     return p->monotonicity == TTM_MONO_SEPARABLE && u_on(p) && p->u_h_cls >= 1 && p->u_h_cls <= 4 &&
-           (p->u_h_ng == 2 || p->u_h_ng == 4 || p->u_p_lag > 2) && all_fast(p, k0, k1) && T <= 4096 && nb <= 65535 && N < ((int64_t)1 << 28) &&
+           (p->u_h_ng == 2 || p->u_h_ng == 4 || p->u_p_lag > 2) && all_fast(p, k0, k1) && N < ((int64_t)1 << 28) &&
            !tn.rt_off && !tn.u_no_hot && (N >= 64 * 1024 || tn.u_loader == 1);
+}
+static bool rt_inverse_gate(const ttm_program* p, int k0, int k1, int64_t N, int T, int nb) {
+    return rt_shape_gate(p, k0, k1, N) && T <= 4096 && nb <= 65535;
 }
 
 // ... and the band kernels among them (csrc/ttm_band.hip; clipped searches only, which the caller checks)
 static bool band_inverse_gate(const ttm_program* p, int k0, int k1, int64_t N, int T, int nb) {
     return rt_inverse_gate(p, k0, k1, N, T, nb) && tuning().band_inv != 0 && ttm_band::usable(p, k0, k1);
+}
+
+// Does ttm_inverse_newton take the push-form root search (k_band_newton / k_band_few_newton)?  The table path's gate without
+// its table geometry: the search reads the fold's U section and nothing else.
+static bool band_newton_gate(const ttm_program* p, int k0, int k1, int64_t N) {
+    return rt_shape_gate(p, k0, k1, N) && tuning().band_newton != 0 && ttm_band::usable(p, k0, k1);
 }
 
 int64_t ttm_fold_size(const ttm_program* p) {
@@ -3746,6 +3756,13 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
         const char* name = nullptr;
         if (ttm_int::root(p, dev_prog(p), k0, k1, coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, nullptr, 1, int_grid_for(N, bd), bd, lds_bytes(ns, bd, 0),
                           tuning().int_xprog == 2, stream, &name) == TTM_OK)
+            return check_launch(name);
+    }
+    // banded separable maps: the same search in push form (csrc/ttm_band.hip); a declined call runs the generic kernel
+    if (band_newton_gate(p, k0, k1, N)) {
+        const char* name = nullptr;
+        if (ttm_band::newton(p, fold + fold_base_size(p), k0, k1, Zsoa, ldz, Xsoa, ldx, N, iters, band_cus(), device_info().lds_per_cu,
+                             tuning().rt_block, stream, &name) == 0)
             return check_launch(name);
     }
     auto kern = p->monotonicity == TTM_MONO_SEPARABLE ? k_inverse_bisect<TTM_MONO_SEPARABLE, true> : k_inverse_bisect<TTM_MONO_INTEGRATED, true>;

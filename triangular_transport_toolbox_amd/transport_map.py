@@ -444,9 +444,19 @@ class transport_map():
     # 320 MB result (tools/pcie_probe.py: 5.6 ms per direction, 6.6 ms for both at once).
     PIPE_MIN_ROWS = 1 << 18          # below this the plain path (one copy in, one copy out)
     PIPE_CHUNKS = 8
+    # rows from which ttm_inverse_newton takes the push-form kernels of banded maps (csrc/ttm_kernels.hip: rt_shape_gate,
+    # N >= 64 * 1024 - keep the two together): a pipelined Newton inverse keeps every chunk at or above it
+    NEWTON_BAND_MIN_ROWS = 64 * 1024
 
     def _pipe_ok(self, N):
         return self._dev.type == 'cuda' and self.host_pipeline and N >= self.PIPE_MIN_ROWS and self._dist() is None
+
+    def _pipe_bounds(self, N):
+        """The chunks of rows [r0, r1) the pipeline cuts N rows into."""
+        nchunk = max(1, min(self.PIPE_CHUNKS, N // (self.PIPE_MIN_ROWS // 2)))
+        rows = -(-N // nchunk)
+        rows = -(-rows // 4096) * 4096                      # (whole tiles: every chunk starts on an even, 32 KB aligned row)
+        return [(r0, min(N, r0 + rows)) for r0 in range(0, N, rows)]
 
     def _host_pipeline(self, Xhost, dout, stage):
         """out[r0:r0+n] = stage(rows (n x d_in row-major device tensor), r0, n) for every chunk of rows of the host matrix
@@ -459,10 +469,8 @@ class transport_map():
             streams = self._pipe_streams = (torch.cuda.Stream(device=self._dev), torch.cuda.Stream(device=self._dev))
         s_in, s_out = streams
         cur = torch.cuda.current_stream(self._dev)
-        nchunk = max(1, min(self.PIPE_CHUNKS, N // (self.PIPE_MIN_ROWS // 2)))
-        rows = -(-N // nchunk)
-        rows = -(-rows // 4096) * 4096                      # (whole tiles: every chunk starts on an even, 32 KB aligned row)
-        bounds = [(r0, min(N, r0 + rows)) for r0 in range(0, N, rows)]
+        bounds = self._pipe_bounds(N)
+        rows = bounds[0][1] - bounds[0][0]
         rows_dev = self._empty(N, d_in)
         out_pin = torch.empty((N, dout), dtype=torch.float64, pin_memory=True)
         # a pageable source does not overlap with anything (the runtime stages it synchronously: H2D + D2H took their sum): the
@@ -1348,23 +1356,39 @@ class transport_map():
         if Z.shape[-1] < ncomp:
             raise IndexError('Z has %d columns, %d are needed' % (Z.shape[-1], ncomp))
         coef = self._pack_coeffs()
-        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
-        if table and Xstar_cols is None and Z.shape[1] == ncomp and Z.flags.c_contiguous and self._pipe_ok(N):
-            # rows are independent in the table inverse (no sample-0 guard): chunks of rows stream through
-            # layout change -> lookups -> layout change back while their neighbours cross PCIe
+        separable = self.monotonicity.lower() == 'separable monotonicity'
+        table = self.alternate_root_finding and separable
+        # the Newton search of a separable map - banded or not: the generic kernel's rows are independent too - has no sample-0
+        # guard and no all-reduce of `iters` either; its chunks must all be large enough for the kernel the whole ensemble would
+        # take (NEWTON_BAND_MIN_ROWS), so that the pipeline returns what the one-copy path returns
+        newton = not table and separable and self.root_finder == 'newton'
+        if (table or newton) and Xstar_cols is None and Z.shape[1] == ncomp and Z.flags.c_contiguous and self._pipe_ok(N) and \
+                (table or min(r1 - r0 for r0, r1 in self._pipe_bounds(N)) >= self.NEWTON_BAND_MIN_ROWS):
+            # rows are independent in the table inverse and the Newton search (no sample-0 guard): chunks of rows stream
+            # through layout change -> lookups / searches -> layout change back while their neighbours cross PCIe
             st = self._stream()
             Xs, Zs = self._cols(d, N, zero=True), self._cols(ncomp, N)
-            self._inverse_table(coef, k0, k1, Zs, Xs, 0)            # (tables of this coefficient vector: built once, no rows)
+            iters = None
+            if table:
+                self._inverse_table(coef, k0, k1, Zs, Xs, 0)        # (tables of this coefficient vector: built once, no rows)
+            else:
+                iters = self._zeros(ncomp, dtype=torch.int32)       # (no tables on this path; one counter for all chunks)
             mean = self._mean_d if self.standardize_samples else None
             sd = self._std_d if self.standardize_samples else None
 
             def stage(rows, r0, n):
                 _capi.check(self._lib.ttm_import(self._ptr(rows), n, ncomp, None, None, self._ptr(Zs, r0), Zs.shape[1], st))
-                self._inverse_table(coef, k0, k1, Zs, Xs, n, row0=r0)
+                if table:
+                    self._inverse_table(coef, k0, k1, Zs, Xs, n, row0=r0)
+                else:
+                    self._inverse_bisect(coef, k0, k1, Zs, Xs, n, row0=r0, iters=iters)
                 out = self._empty(n, d)
                 _capi.check(self._lib.ttm_export(self._ptr(Xs, r0), Xs.shape[1], n, 0, d, self._ptr(mean), self._ptr(sd), self._ptr(out), st))
                 return out
-            return self._host_pipeline(Z, d, stage)[:, skip:]
+            X = self._host_pipeline(Z, d, stage)
+            if iters is not None and self.verbose and int(iters.max().item()) >= 100:
+                print('WARNING: root search stopped at maximum iterations.')
+            return X[:, skip:]
         Xs = self._cols(d, N, zero=True)
         if Xstar_cols is not None and E > 0:
             cols = np.array(Xstar_cols, dtype=float, copy=True)
@@ -1449,23 +1473,27 @@ class transport_map():
                                                 self._ptr(tab_y_d), resolution, resolution, None, self._ptr(tmin_d),
                                                 self._ptr(tmax_d), ctypes.c_void_p(bkt_d.data_ptr()), nb, trunc, None, 0, st))
 
-    def _inverse_bisect(self, coef, k0, k1, Zs, Xs, N):
+    def _inverse_bisect(self, coef, k0, k1, Zs, Xs, N, row0=0, iters=None):
         """TM:3798-3985.  Samples 1..N-1 run to convergence and record the largest
         midpoint-iteration count per component; global sample 0 is then replayed
         with that count as its cap, which is what the reference's
         ``while np.sum(indices) > 0`` guard (TM:3952) does to it.
         With ``root_finder = 'newton'`` (an extension, off by default): safeguarded Newton steps inside the same
         bracket and with the same stopping rule - the same roots to |S - z| <= 1e-9 in a fifth of the evaluations,
-        not the reference's last midpoints and without its sample-0 quirk."""
+        not the reference's last midpoints and without its sample-0 quirk.  Rows are independent there: `row0` / `iters`
+        let the host pipeline send chunks of rows with one counter, which it reads after the last chunk."""
         torch = _torch()
         ncomp = k1 - k0
-        iters = self._zeros(ncomp, dtype=torch.int32)
         if self.root_finder == 'newton':
-            _capi.check(self._lib.ttm_inverse_newton(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), k0, k1, self._ptr(Zs), Zs.shape[1],
-                                                     self._ptr(Xs), Xs.shape[1], N, ctypes.c_void_p(iters.data_ptr()), self._stream()))
-            if self.verbose and int(iters.max().item()) >= 100:
+            own = iters is None
+            if own:
+                iters = self._zeros(ncomp, dtype=torch.int32)
+            _capi.check(self._lib.ttm_inverse_newton(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), k0, k1, self._ptr(Zs, row0), Zs.shape[1],
+                                                     self._ptr(Xs, row0), Xs.shape[1], N, ctypes.c_void_p(iters.data_ptr()), self._stream()))
+            if own and self.verbose and int(iters.max().item()) >= 100:
                 print('WARNING: root search stopped at maximum iterations.')
             return
+        iters = self._zeros(ncomp, dtype=torch.int32)
         dist = self._dist()
         owns_first = dist is None or dist.get_rank() == 0
         first = 1 if owns_first else 0
