@@ -1,11 +1,12 @@
 // ttm_band.h - internal interface of csrc/ttm_band.hip (the kernels of banded U-form maps) to csrc/ttm_kernels.hip.
 //
 // A BANDED map (BASELINE config 5, Markov-type maps): the columns of the components are consecutive and every
-// nonmonotone group of component k reads a column kc-1 .. kc-LAG (LAG <= TTM_P_LAG_MAX), every component has a
-// special-term spline and no polynomial terms of its own variable.  Such a map is evaluated in PUSH form: walking the
+// nonmonotone group of component k reads a column kc-1 .. kc-LAG (LAG <= TTM_P_LAG_MAX), the monotone part of every
+// component is a special-term spline, one linear term of its own variable, or both (no other polynomial / Hermite-function
+// terms of the own variable).  Such a map is evaluated in PUSH form: walking the
 // columns in order, the value x_c of a column is used at once for everything that depends on it -
 //
-//     S at column c          = pend[0] + G_c(x_c)                      (G_c: the component's spline)
+//     S at column c          = pend[0] + own1_c x_c + G_c(x_c)         (G_c: the component's spline, own1_c: slope of its linear term)
 //     pend[l], l = 0..LAG-2  = pend[l+1] + f_{c+l+1, c}(x_c)           (contribution to the component l+1 columns on)
 //     pend[LAG-1]            = c0_{c+LAG} + f_{c+LAG, c}(x_c)
 //
@@ -42,8 +43,8 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
             int nb, const double* img, int img_doubles, int cus, size_t lds_per_cu, int window, int block, void* stream, const char** kernel_name);
 
 // safeguarded Newton root search (sample_newton, csrc/ttm_eval.h: bracket +-2, window doubling, |S - z| <= 1e-9, at most 100
-// trial points) in push form: the monotone part is the component's resident spline (+ the linear own term of a map of a few
-// components), no tables.  Conditioning columns (if any) are read from Xsoa.  iters: as ttm_inverse_newton.  1: declined
+// trial points) in push form: the monotone part is the component's resident spline (+ its linear own term), no
+// tables.  Conditioning columns (if any) are read from Xsoa.  iters: as ttm_inverse_newton.  1: declined
 int newton(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
            int32_t* iters, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name);
 

@@ -244,8 +244,9 @@ __device__ __forceinline__ double band_spline(const double* tab, int nI, double 
 // ---------------------------------------------------------------------------
 // forward map
 // ---------------------------------------------------------------------------
-// the columns [kb, ke) of one tile; FULL: every row of the tile exists (unmasked stores)
-template <int CLS, int LAG, bool FULL>
+// the columns [kb, ke) of one tile; FULL: every row of the tile exists (unmasked stores); OWN: some component of the map has
+// a linear term of its own variable next to its spline or instead of it (slot [7] of the record; NI = 0: no spline)
+template <int CLS, int LAG, bool FULL, bool OWN>
 __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const double* etab, const double* tabs, int tab0, int kb, int ke,
                                                   const char* xcol, int64_t ldxb, char* zcol, int64_t ldzb, unsigned int tbase,
                                                   const unsigned int (&roff)[BAND_NS / 2], unsigned int c1_32,
@@ -273,6 +274,7 @@ __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const dou
         __builtin_amdgcn_sched_barrier(0);                    // (the scheduler would sink the loads to the end of the step)
         // ---- uniform data of the step ------------------------------------------------------------------------
         const double start = rec[0], sp_a = rec[2], sp_b = rec[3], sp_ds = rec[4];
+        const double own1 = OWN ? rec[7] : 0.0;
         cint_p ri = (cint_p)rec;
         const int nI = ri[10];
         const double* tab = tabs + (ri[11] - tab0);
@@ -285,9 +287,9 @@ __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const dou
             for (int h = 0; h < 2; ++h) {
                 const int e = 2 * q + h;
                 const double x = h ? xc[q].y : xc[q].x;
-                const double m = band_spline(tab, nI, sp_a, sp_b, sp_ds, x);
+                const double m = (!OWN || nI > 0) ? band_spline(tab, nI, sp_a, sp_b, sp_ds, x) : 0.0;
                 const double E = band_expq(etab, x, kt);
-                zv[h] = pend[e][0] + m;
+                zv[h] = OWN ? fma(own1, x, pend[e][0] + m) : pend[e][0] + m;     // (x 0 too: a NaN / infinite sample stays NaN)
                 band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, x, E, pend[e]);
             }
             const unsigned int n = tbase + (unsigned int)(q * HALF);
@@ -368,7 +370,7 @@ __device__ __forceinline__ void band_spline_d(const double* tab, int nI, double 
 #define BAND_LD_CHUNK 2
 #define BAND_UNI 256                                  /* components of a density pass, at most */
 #define BAND_DENS_NS 4
-template <int CLS, int LAG, bool WRITE_Z>
+template <int CLS, int LAG, bool WRITE_Z, bool OWN>
 __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                           const double* __restrict__ X, int64_t ldx, int64_t N,
                                                           double* __restrict__ Z, int64_t ldz, double* __restrict__ logdet,
@@ -377,8 +379,10 @@ __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restri
     constexpr int DB = cls_db(CLS), DA = cls_da(CLS), PS = rec_stride(CLS, LAG);
     // (two rows per thread: the pass carries three more running values per row than the plain map and is bound by its
     // arithmetic, not by the column stream)
-    // (four rows per thread without Z; with it the masked stores of every step copy leave registers for two)
-    constexpr int NS = WRITE_Z ? 2 : BAND_DENS_NS, NP = NS / 2, CT = BAND_CT, ROWS = NS * CT, HALF = 2 * CT;
+    // (four rows per thread without Z; with it the masked stores of every step copy leave registers for two - and so does the
+    // own term: slope, the branch around a missing spline and the derivative formed per evaluation spill ~280 registers at four)
+    constexpr bool SHORT = WRITE_Z || OWN;                // two rows per thread, two columns per trip of the column loop
+    constexpr int NS = SHORT ? 2 : BAND_DENS_NS, NP = NS / 2, CT = BAND_CT, ROWS = NS * CT, HALF = 2 * CT;
     extern __shared__ __align__(16) double g_lds[];
     double* etab = g_lds;
     double* tabs = g_lds + BAND_ET_DOUBLES;
@@ -394,13 +398,14 @@ __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restri
     const unsigned int c1_32 = (unsigned int)c1;
     const int64_t ldxb = ldx * 8, ldzb = ldz * 8;
     // uniform part of the log-determinant: sum_k log(2 / h_k) - sum_k log(sigma_k): one logarithm per thread, summed in
-    // component order by thread 0 (every thread taking all of them was a fifth of the launch)
+    // component order by thread 0 (every thread taking all of them was a fifth of the launch).  OWN: dS_k/dx_k =
+    // dm 2 / h_k + own1 has no uniform factor - the 2 / h_k are applied per evaluation, as k_band_few does
     __shared__ double s_uni[BAND_UNI];
     double luni;
     {
         const int ncomp = k1 - k0;
         for (int k = tid; k < ncomp; k += CT) {
-            double v = band_log(P[(int64_t)(k0 + k + LAG) * PS + 4]);
+            double v = OWN ? 0.0 : band_log(P[(int64_t)(k0 + k + LAG) * PS + 4]);
             if (sigma) v -= band_log(sigma[k]);
             s_uni[k] = v;
         }
@@ -479,6 +484,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restri
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const double start = rec[0], sp_a = rec[2], sp_b = rec[3], sp_ds = rec[4];
+                const double own1 = OWN ? rec[7] : 0.0;
                 cint_p ri = (cint_p)rec;
                 const int nI = ri[10];
                 const double* tab = tabs + (ri[11] - tab0);
@@ -489,10 +495,11 @@ __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restri
                     for (int h = 0; h < 2; ++h) {
                         const int e = 2 * q + h;
                         const double x = h ? xc[q].y : xc[q].x;
-                        double m, dm;
-                        band_spline_d(tab, nI, sp_a, sp_b, sp_ds, x, m, dm);
+                        double m = 0.0, dm = 0.0;
+                        if (!OWN || nI > 0) band_spline_d(tab, nI, sp_a, sp_b, sp_ds, x, m, dm);
                         const double E = band_expq(etab, x, kt);
-                        zv[h] = pend[e][0] + m;
+                        zv[h] = OWN ? fma(own1, x, pend[e][0] + m) : pend[e][0] + m;
+                        if (OWN) dm = fma(dm, sp_ds, fma(x, 0.0, own1));      // dS_k/dx_k (x 0: a NaN / infinite sample stays NaN)
                         ss[e] = fma(zv[h], zv[h], ss[e]);
                         prod[e] *= dm;
                         dmin[e] = fmin(dmin[e], dm);
@@ -506,7 +513,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restri
                         else if (n < c1_32) *(double*)zp = zv[0];
                     }
                 }
-                if (WRITE_Z && (((j - k0) & (BAND_LD_CHUNK - 1)) == BAND_LD_CHUNK - 1)) {
+                if (SHORT && (((j - k0) & (BAND_LD_CHUNK - 1)) == BAND_LD_CHUNK - 1)) {
 #pragma unroll
                     for (int e = 0; e < NS; ++e) { int ex; prod[e] = frexp(prod[e], &ex); pexp[e] += ex; }
                 }
@@ -520,7 +527,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_density(const double* __restri
                 for (int e = 0; e < NS; ++e) { int ex; prod[e] = frexp(prod[e], &ex); pexp[e] += ex; }
             };
             int j = kb;
-            if (WRITE_Z) {                                    // (fewer step copies: two columns at a time)
+            if (SHORT) {                                      // (fewer step copies: two columns at a time)
                 for (; j + 1 < ke; j += 2) {
                     step(j, xa, xb);
                     step(j + 1, xb, xa);
@@ -768,7 +775,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_logdet(const double* __restric
 }
 
 // LDS: [E table: 2 x 801 | splines of the block's components, as they stand in the U section]
-template <int CLS, int LAG>
+template <int CLS, int LAG, bool OWN>
 __global__ __launch_bounds__(BAND_CT) void k_band_forward(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                           const double* __restrict__ X, int64_t ldx, int64_t N,
                                                           double* __restrict__ Z, int64_t ldz, int64_t rows_per_wg, int Bc) {
@@ -837,8 +844,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_forward(const double* __restri
             }
             const char* xcol = (const char*)X + (int64_t)colb * ldxb;
             char* zcol = (char*)Z + (int64_t)(kb - k0) * ldzb;
-            if (full) band_forward_tile<CLS, LAG, true>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
-            else band_forward_tile<CLS, LAG, false>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
+            if (full) band_forward_tile<CLS, LAG, true, OWN>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
+            else band_forward_tile<CLS, LAG, false, OWN>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
         }
     }
 }
@@ -2308,7 +2315,7 @@ __device__ __forceinline__ void band_iters_max(int* iters, int c, int it) {
 // (its own stores, or conditioning columns) and pushes them again with the same arithmetic: a row's result does not depend on
 // the chunking.  A pair whose second row does not exist (odd N) carries its first row twice: padding never enters a search.
 // LDS: [E table: 2 x 801 | splines of the block's components, as they stand in the U section]
-template <int CLS, int LAG>
+template <int CLS, int LAG, bool OWN>
 __global__ __launch_bounds__(BAND_CT) void k_band_newton(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                          const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
                                                          int* __restrict__ iters, int64_t rows_per_wg, int Bc) {
@@ -2395,11 +2402,13 @@ __global__ __launch_bounds__(BAND_CT) void k_band_newton(const double* __restric
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const double start = rec[0], sp_a = rec[2], sp_b = rec[3], sp_ds = rec[4];
+                const double own1 = OWN ? rec[7] : 0.0;
                 cint_p ri = (cint_p)rec;
-                const int nI = ri[10];
+                const int nI = ri[10];                        // (OWN: 0 - no special terms, no spline: the component is linear)
                 const double* tab = tabs + (ri[11] - tab0);
                 auto sp = [&](auto der, double x, double& g, double& dg) {
-                    if (decltype(der)::value) band_spline_d(tab, nI, sp_a, sp_b, sp_ds, x, g, dg);
+                    if (OWN && nI <= 0) { g = 0.0; dg = 0.0; }
+                    else if (decltype(der)::value) band_spline_d(tab, nI, sp_a, sp_b, sp_ds, x, g, dg);
                     else { g = band_spline(tab, nI, sp_a, sp_b, sp_ds, x); dg = 0.0; }
                 };
                 // (rows of the tile beyond the chunk belong to the next workgroup: not searched, not counted, not stored)
@@ -2410,7 +2419,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_newton(const double* __restric
                     tg[e] = ((e & 1) ? zc[e >> 1].y : zc[e >> 1].x) - pend[e][0];
                     live[e] = full || tbase + (unsigned int)((e >> 1) * HALF + (e & 1)) < c1_32;
                 }
-                const int it = band_newton_rows<NS, false>(sp, 0.0, sp_ds, tg, live, r);
+                const int it = band_newton_rows<NS, OWN>(sp, own1, sp_ds, tg, live, r);
                 // x_c is pushed on to the components that read it, and stored
 #pragma unroll
                 for (int e = 0; e < NS; ++e) band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, r[e], band_expq_far(etab, r[e], kt), pend[e]);
@@ -2624,15 +2633,24 @@ int build_records(const ttm_program* p, double* U, void* stream) {
     return 0;
 }
 
-// components per block so that the splines of a block fit `budget` bytes (0: not even one)
+// does a component of [k0, k1) have a linear term of its own variable (slot [7] of its push record; it may then have no spline)?
+static bool sweep_has_own(const ttm_program* p, int k0, int k1) {
+    for (int k = k0; k < k1; ++k)
+        if (p->h_ucomp[k * TTM_UC_LEN + TTM_UC_FLAGS] & TTM_UCF_OWN) return true;
+    return false;
+}
+
+// components per block so that the splines of a block fit `budget` bytes (0: not even one).  A sweep without any spline
+// (linear monotone parts) is one block that stages nothing.
 static int plan_blocks(const ttm_program* p, int k0, int k1, size_t budget, int* nblk_out) {
     int worst = 0;
     for (int k = k0; k < k1; ++k) {
         const int b = p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI] * TTM_U_TSTRIDE * 8;
         worst = b > worst ? b : worst;
     }
-    if (worst <= 0 || (size_t)worst > budget) return 0;
     const int ncomp = k1 - k0;
+    if (worst <= 0) { *nblk_out = 1; return ncomp; }
+    if ((size_t)worst > budget) return 0;
     for (int nblk = 1; nblk <= ncomp; ++nblk) {
         const int Bc = (ncomp + nblk - 1) / nblk;
         bool ok = true;
@@ -2659,14 +2677,7 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
     if (lds_per_cu <= fixed) return 1;
     int nblk = 0;
     int Bc = plan_blocks(p, k0, k1, lds_per_cu - fixed, &nblk);
-    if (Bc <= 0) {
-        // a sweep without any spline (linear monotone parts: the smoother's block map) of a few components: one block, no tables
-        bool any = false;
-        for (int k = k0; k < k1; ++k) any = any || p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI] > 0;
-        if (any || k1 - k0 > TTM_P_FEW_D) return 1;
-        Bc = k1 - k0;
-        nblk = 1;
-    }
+    if (Bc <= 0) return 1;
     if (block > 0 && block < Bc) Bc = block;
     size_t lds = 0;
     for (int kb = k0; kb < k1; kb += Bc) {
@@ -2680,11 +2691,6 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
         const size_t lbudget = lds_per_cu - (size_t)BAND_UNI * 8;
         int lblk = 0;
         int LBc = plan_blocks(p, k0, k1, lbudget, &lblk);
-        if (LBc <= 0) {                                       // (a range without any spline: one block)
-            bool any = false;
-            for (int k = k0; k < k1; ++k) any = any || p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI] > 0;
-            if (!any) LBc = k1 - k0;
-        }
         if (LBc > 0) {
             if (block > 0 && block < LBc) LBc = block;
             size_t llds = 16;
@@ -2752,11 +2758,14 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
         }
     }
     if (p->u_p_lag != 2 || cls > 3) return 1;             // (lag-3 records / order class 4: the few-component kernels only)
+    // (a map without linear own terms takes the instantiations without them: no slot [7], no test for a missing spline)
+    const bool own = sweep_has_own(p, k0, k1);
     if (logdet || sumsq) {
         typedef void (*dkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, int64_t, double*, int64_t, double*, const double*,
                                 double*, int64_t, int);
-        dkern_t dk = Zsoa ? (p->u_h_cls == 1 ? k_band_density<1, 2, true> : p->u_h_cls == 2 ? k_band_density<2, 2, true> : k_band_density<3, 2, true>)
-                          : (p->u_h_cls == 1 ? k_band_density<1, 2, false> : p->u_h_cls == 2 ? k_band_density<2, 2, false> : k_band_density<3, 2, false>);
+#define BAND_DENS_K(WZ, OW) (cls == 1 ? k_band_density<1, 2, WZ, OW> : cls == 2 ? k_band_density<2, 2, WZ, OW> : k_band_density<3, 2, WZ, OW>)
+        dkern_t dk = Zsoa ? (own ? BAND_DENS_K(true, true) : BAND_DENS_K(true, false)) : (own ? BAND_DENS_K(false, true) : BAND_DENS_K(false, false));
+#undef BAND_DENS_K
         const int64_t rows = chunk_rows(N, cus);
         const int64_t grid = (N + rows - 1) / rows;
         allow_lds((const void*)dk, lds);
@@ -2766,7 +2775,8 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
         return 0;
     }
     typedef void (*kern_t)(const double*, int64_t, int, int, int, const double*, int64_t, int64_t, double*, int64_t, int64_t, int);
-    kern_t kern = p->u_h_cls == 1 ? k_band_forward<1, 2> : p->u_h_cls == 2 ? k_band_forward<2, 2> : k_band_forward<3, 2>;
+    kern_t kern = own ? (cls == 1 ? k_band_forward<1, 2, true> : cls == 2 ? k_band_forward<2, 2, true> : k_band_forward<3, 2, true>)
+                      : (cls == 1 ? k_band_forward<1, 2, false> : cls == 2 ? k_band_forward<2, 2, false> : k_band_forward<3, 2, false>);
     const int64_t rows = chunk_rows(N, cus);
     const int64_t grid = (N + rows - 1) / rows;
     allow_lds((const void*)kern, lds);
@@ -2868,8 +2878,6 @@ int newton(const ttm_program* p, const double* U, int k0, int k1, const double* 
         }
     }
     if (lag != 2 || cls > 3) return 1;                        // (lag-3 records / order class 4: the few-component kernel only)
-    for (int k = k0; k < k1; ++k)
-        if (p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI] <= 0) return 1;             // (every component of a long sweep has its spline)
     const size_t fixed = (size_t)BAND_ET_DOUBLES * 8;
     if (lds_per_cu <= fixed) return 1;
     int nblk = 0;
@@ -2887,7 +2895,9 @@ int newton(const ttm_program* p, const double* U, int k0, int k1, const double* 
     lds += fixed;
     if (lds > lds_per_cu) return 1;
     typedef void (*kern_t)(const double*, int64_t, int, int, int, const double*, int64_t, double*, int64_t, int64_t, int*, int64_t, int);
-    kern_t kern = cls == 1 ? k_band_newton<1, 2> : cls == 2 ? k_band_newton<2, 2> : k_band_newton<3, 2>;
+    // (a map without linear own terms takes the instantiations without them)
+    kern_t kern = sweep_has_own(p, k0, k1) ? (cls == 1 ? k_band_newton<1, 2, true> : cls == 2 ? k_band_newton<2, 2, true> : k_band_newton<3, 2, true>)
+                                           : (cls == 1 ? k_band_newton<1, 2, false> : cls == 2 ? k_band_newton<2, 2, false> : k_band_newton<3, 2, false>);
     const int64_t rows = chunk_rows(N, cus);
     const int64_t grid = (N + rows - 1) / rows;
     allow_lds((const void*)kern, lds);

@@ -3199,6 +3199,13 @@ static bool band_forward_gate(const ttm_program* p, int k0, int k1, int64_t N) {
            !tn.u_no_hot && (N >= 64 * 1024 || tn.band_fwd == 1) && ttm_band::usable(p, k0, k1);
 }
 
+// Can the hot-record kernels (k_forward_hl, k_inverse_rt) sweep the hot records of this map themselves?  They are instantiated
+// for records of 2 and 4 groups without an own term; records of TTM_H_NG_MAX groups (maps of a few components with five groups,
+// banded maps with linear own terms) and those of lag-3 / lag-5 maps only feed the push records (include/ttm.h).
+static bool hot_sweepable(const ttm_program* p) {
+    return p->u_h_cls >= 1 && p->u_h_cls <= 3 && (p->u_h_ng == 2 || p->u_h_ng == 4) && p->u_p_lag <= 2;
+}
+
 // Does ttm_inverse_table take the resident-table kernels (k_inverse_rt, and the band kernels where band_inverse_gate holds)
 // for [k0, k1) at N samples and this table geometry?  Shape and options only: the caller checks that the tables come with an
 // affine abscissa (h_y_affine, ldy = 0).  (Small ensembles: the table load per workgroup does not pay; option u_loader = 1
@@ -3207,7 +3214,7 @@ static bool band_forward_gate(const ttm_program* p, int k0, int k1, int64_t N) {
 static bool rt_shape_gate(const ttm_program* p, int k0, int k1, int64_t N) {
     const Tuning& tn = tuning();
     return p->monotonicity == TTM_MONO_SEPARABLE && u_on(p) && p->u_h_cls >= 1 && p->u_h_cls <= 4 &&
-           (p->u_h_ng == 2 || p->u_h_ng == 4 || p->u_p_lag > 2) && all_fast(p, k0, k1) && N < ((int64_t)1 << 28) &&
+           (hot_sweepable(p) || p->u_p_lag >= 2) && all_fast(p, k0, k1) && N < ((int64_t)1 << 28) &&
            !tn.rt_off && !tn.u_no_hot && (N >= 64 * 1024 || tn.u_loader == 1);
 }
 static bool rt_inverse_gate(const ttm_program* p, int k0, int k1, int64_t N, int T, int nb) {
@@ -3342,8 +3349,7 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
             // samples interleave to that rate; with two the chains wait on themselves)
             int hNS = 4;
             if (tn.hl_ns > 0) hNS = tn.hl_ns == 4 ? 4 : 2;
-            const bool hot = p->u_h_cls >= 1 && p->u_h_cls <= 3 && (p->u_h_ng == 2 || p->u_h_ng == 4) && !tn.u_no_hot &&
-                             p->u_p_lag <= 2;                          // (lag-3 maps: hot records without cache hits, include/ttm.h)
+            const bool hot = hot_sweepable(p) && !tn.u_no_hot;          // (not: records that only feed the push records, include/ttm.h)
             const int hcw = TTM_HL_FWD_CW(logdet != nullptr);            // evaluating waves per workgroup of the hot kernel
             const int rows = hot ? hcw * 64 * hNS : TTM_UL_ROWS;
             auto lds_for = [&](int xl, int tl) { return ((size_t)(xl + 1) * rows + (size_t)(tl + 1) * tab_slot + (size_t)2 * ways * rows + TTM_EXPQ_TABLE_LEN) * 8; };
@@ -3614,7 +3620,7 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
     }
     // k_inverse_rt sweeps the hot records themselves: not for lag-3 maps (include/ttm.h), and with fewer than four
     // components its table load per workgroup does not pay (order class 4: the few-component kernels only)
-    if (affine && rt_inverse_gate(p, k0, k1, N, T, nb) && p->u_p_lag <= 2 && p->u_h_cls <= 3 && (k1 - k0 >= 4 || tn.u_loader == 1)) {
+    if (affine && rt_inverse_gate(p, k0, k1, N, T, nb) && hot_sweepable(p) && (k1 - k0 >= 4 || tn.u_loader == 1)) {
         const DeviceInfo& di = device_info();
         const int ways = plan_ways_of(p);
         const int ncomp = k1 - k0;

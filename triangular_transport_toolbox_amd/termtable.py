@@ -897,33 +897,38 @@ def _compile_uform(cm, u_info, polyclass, separable):
                 ma = max(ma, (fl >> 24) & 15)
     ng = int(max(ucomp[:, 2], default=0))
     # banded map (include/ttm.h "push records"): consecutive columns, every group reads one of the P_LAG_MAX columns in
-    # front of its component, a spline in every component -> csrc/ttm_band.hip.  Records for lag 2 (what the kernels of
-    # large maps are instantiated for) unless a group reaches three columns back, which only the kernels of maps with a
-    # few components (P_FEW_D) take.
+    # front of its component, a monotone part of a spline and / or one linear own term -> csrc/ttm_band.hip.  Records for
+    # lag 2 (what the kernels of large maps are instantiated for) unless a group reaches three columns back, which only the
+    # kernels of maps with a few components (P_FEW_D) take.
     kc0 = int(ucomp[0, 0]) if cm.D else 0
     lags = [int(ucomp[k, 0]) - int(ugrp[int(ucomp[k, 3]) + g, 0]) for k in range(cm.D) for g in range(int(ucomp[k, 2]))]
     maxlag = max(lags, default=1)
-    # the monotone part of a component: its special-term spline, and for maps of a few components possibly ONE linear term
-    # of its own variable next to it (or instead of it: the [k] terms of examples 05 / 06 / 07) - the push record carries
-    # that coefficient; other polynomial / Hermite-function terms of the own variable stay with the generic kernels
+    # the monotone part of a component: its special-term spline, possibly ONE linear term of its own variable next to it
+    # (or instead of it: the [k] terms of examples 05 / 06 / 07, the order-1 filter map) - the push record carries that
+    # coefficient; other polynomial / Hermite-function terms of the own variable stay with the generic kernels
     own = [bool(int(f) & UCF_OWN) for f in ucomp[:, 7]]
     own_linear = [o and u['maxP_hf'] == 0 and u['maxP_poly'] == 1 for o, u in zip(own, u_info)]
     few = cm.D <= P_FEW_D
     banded = cm.D >= 1 and all(int(ucomp[k, 0]) == kc0 + k for k in range(cm.D)) and all(lag >= 1 for lag in lags) and \
         (maxlag <= 2 or (maxlag <= P_LAG_MAX and few)) and \
-        all((len(u['st_p0']) > 0 and not o) or (few and ol) for u, o, ol in zip(u_info, own, own_linear)) and \
-        (any(len(u['st_p0']) > 0 for u in u_info) or few)            # (no spline at all: the smoother's block map, linear monotone parts)
+        all((len(u['st_p0']) > 0 and not o) or ol for u, o, ol in zip(u_info, own, own_linear))
     # (a banded map of a few components whose groups do not all hit the planned column cache - a group three columns back,
     # conditioning columns in front of the first component - or with linear own terms still gets hot records: as the source of
     # its push records only, u_p_lag = 3 says so)
     few_only = banded and few and (maxlag >= 3 or not all_hit or any(own))
+    # (a long banded map with linear own terms likewise: hot records have no slot for an own term, so its records carry
+    # H_NG_MAX group slots - a shape no hot-record kernel is instantiated for - and only feed the lag-2 push records)
+    long_own = banded and not few and all_hit and any(own)
+    feed_only = few_only or long_own
     # (the hot-record kernels are instantiated for 2 and 4 group records; five groups - the third component of the smoother's block
-    # map, example_07.py:368-408 - exist for maps of a few components, whose records only feed the push records)
-    if ((all_hit and not any(own)) or few_only) and ng <= (H_NG_MAX if few_only else 4):
+    # map, example_07.py:368-408 - exist for maps whose records only feed the push records)
+    if ((all_hit and not any(own)) or feed_only) and ng <= (H_NG_MAX if feed_only else 4):
         # (orders 8..10 - class 4, example_03.py:103 - exist for the kernels of maps with a few components only)
         cm.u_h_cls = 1 if (mb <= 3 and ma <= 1) else (2 if (mb <= 5 and ma <= 5) else (3 if (mb <= 7 and ma <= 7) else (4 if (banded and few) else 0)))
     if cm.u_h_cls:
         cm.u_h_ng = 2 if ng <= 2 else (4 if ng <= 4 else H_NG_MAX)        # the kernels are instantiated for 2 and 4 group records
+        if long_own:
+            cm.u_h_ng = H_NG_MAX
         if banded:
             cm.u_p_lag = (3 if maxlag <= 3 else P_LAG_MAX) if few_only else 2
             gp = H_DB[cm.u_h_cls] + 1 + H_DA[cm.u_h_cls]
