@@ -2581,6 +2581,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_newton(const double* __res
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+static_assert(BAND_RT_KMAX == BAND_RING_KMAX, "k_band_inverse and the ring plan (ttm_band_image.h) cap a block at the same number of components");
+
 static void allow_lds(const void* kern, size_t bytes) {
     static thread_local const void* seen[16];
     static thread_local size_t granted[16];
@@ -2596,12 +2598,61 @@ static void allow_lds(const void* kern, size_t bytes) {
     if (n < 16) { seen[n] = kern; granted[n] = bytes; ++n; }
 }
 
+// the tail of every entry point: BAND_CT threads per workgroup, `lds` bytes of dynamic LDS, the kernel's name for the caller
+template <class... P, class... A>
+static int launch(void (*kern)(P...), int64_t grid, size_t lds, void* stream, const char* name, const char** kernel_name, A... args) {
+    allow_lds((const void*)kern, lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BAND_CT), lds, (hipStream_t)stream, static_cast<P>(args)...);
+    if (kernel_name) *kernel_name = name;
+    return 0;
+}
+
+// ---- a run-time value picks a template argument: f gets it as a std::integral_constant and returns the kernel.  Every entry
+// point has checked the ranges (usable(); the long kernels exist for lag 2 and the classes 1..3 only) ----
+template <int V> using int_c = std::integral_constant<int, V>;
+template <int NCLS, class F> static auto with_cls(int cls, F f) {          // degree class 1..NCLS (3: the long kernels, 4: the few-component ones)
+    if (cls == 1) return f(int_c<1>{});
+    if (cls == 2) return f(int_c<2>{});
+    if constexpr (NCLS == 4) { if (cls != 3) return f(int_c<4>{}); }
+    return f(int_c<3>{});
+}
+template <class F> static auto with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> static auto with_lag(int lag, F f) {                    // groups per push record
+    return lag == 5 ? f(int_c<5>{}) : lag == 3 ? f(int_c<3>{}) : f(int_c<2>{});
+}
+// (record lag, reach of the sweep) of the few-component kernels: exactly the pairs they exist for.  Records of five groups - the
+// smoother's block map - have one shape, zeros beyond a sweep's reach
+template <class F> static auto with_reach(int lag, int lage, F f) {
+    if (lag == 5) return f(int_c<5>{}, int_c<5>{});
+    if (lag == 3) return lage == 1 ? f(int_c<3>{}, int_c<1>{}) : lage == 2 ? f(int_c<3>{}, int_c<2>{}) : f(int_c<3>{}, int_c<3>{});
+    return lage == 1 ? f(int_c<2>{}, int_c<1>{}) : f(int_c<2>{}, int_c<2>{});
+}
+
+// ---- buffers ----
+static bool vec_ok(const void* ptr) { return (uintptr_t)ptr % 16 == 0; }   // 16-byte accesses (a null pointer passes: optional buffers)
+// a column-major matrix the kernels read and write two rows at a time; need: (N + 1) & ~1 rows per column, or 0 where the
+// leading dimension is not held against N
+static bool col_ok(const void* ptr, int64_t ld, int64_t need) { return vec_ok(ptr) && ld % 2 == 0 && ld >= need; }
+static int64_t even_rows(int64_t N) { return (N + 1) & ~(int64_t)1; }
+// the table lookups take exp(w) from its Taylor polynomial: |w| <= 0.1 over the tables' range
+static bool y_affine_ok(const double* y) {
+    if (!y) return false;
+    const double ymax = fabs(y[0]) > fabs(y[2]) ? fabs(y[0]) : fabs(y[2]);
+    return y[1] > 0.0 && y[1] * ymax * 0.5 <= 0.1;
+}
+
+// ---- grids ----
 // rows of a workgroup's chunk: N / #CUs rounded up to whole 128-byte lines of a column, so that every wave's 1 KB
 // accesses are line-aligned (a chunk that starts inside a line makes every wave's store touch nine lines, two of them
 // partially: the column stream then runs at 72 % of the copy rate instead of ...: profiles/r03_*)
 static int64_t chunk_rows(int64_t N, int cus) {
     const int64_t rows = (N + cus - 1) / cus;
     return (rows + 31) / 32 * 32;
+}
+struct ChunkGrid { int64_t rows, grid; };            // the long kernels: one chunk of rows per workgroup
+static ChunkGrid chunk_grid(int64_t N, int cus) {
+    const int64_t rows = chunk_rows(N, cus);
+    return {rows, (N + rows - 1) / rows};
 }
 
 int record_stride(int cls, int lag) { return rec_stride(cls, lag); }
@@ -2612,19 +2663,7 @@ bool usable(const ttm_program* p, int k0, int k1) {
            p->h_ucomp && k0 >= 0 && k1 <= p->D && k0 < k1 && p->u_p_stride == rec_stride(p->u_h_cls, p->u_p_lag);
 }
 
-// how far back the groups of the components [k0, k1) reach, and whether any of them has plain polynomial terms
-static void sweep_shape(const ttm_program* p, int k0, int k1, int* lage, bool* plain) {
-    *lage = 1; *plain = false;
-    for (int k = k0; k < k1; ++k) {
-        const int32_t* uc = p->h_ucomp + k * TTM_UC_LEN;
-        for (int g = 0; g < uc[TTM_UC_N_GRP]; ++g) {
-            const int32_t* G = p->h_ugrp + (uc[TTM_UC_GRP_OFF] + g) * TTM_UG_LEN;
-            const int lag = uc[TTM_UC_KC] - G[TTM_UG_VAR];
-            *lage = lag > *lage ? lag : *lage;
-            *plain = *plain || (G[TTM_UG_FLAGS] & TTM_UGF_POLY);
-        }
-    }
-}
+static int uc(const ttm_program* p, int k, int word) { return p->h_ucomp[k * TTM_UC_LEN + word]; }
 
 int build_records(const ttm_program* p, double* U, void* stream) {
     if (!p || !p->u_enabled || p->u_p_lag <= 0 || p->u_h_cls <= 0) return 0;
@@ -2634,156 +2673,152 @@ int build_records(const ttm_program* p, double* U, void* stream) {
 }
 
 // does a component of [k0, k1) have a linear term of its own variable (slot [7] of its push record; it may then have no spline)?
+// (a map without them takes the instantiations without: no slot [7], no test for a missing spline)
 static bool sweep_has_own(const ttm_program* p, int k0, int k1) {
     for (int k = k0; k < k1; ++k)
-        if (p->h_ucomp[k * TTM_UC_LEN + TTM_UC_FLAGS] & TTM_UCF_OWN) return true;
+        if (uc(p, k, TTM_UC_FLAGS) & TTM_UCF_OWN) return true;
     return false;
 }
 
+// ---- the few-component kernels (k_band_few*): everything requested at once, tiles of 2048 rows, a persistent grid ----
+struct FewSweep {
+    int tab0, ntab;                                  // the splines of the sweep as they stand in the U section (padding between them included)
+    bool stageable;                                  // ... and a launch can stage them: whole 16-byte units, two loads per thread
+    size_t lds;                                      // exp table + splines (+ one unit)
+    int lage; bool plain;                            // how far back the groups reach; does any of them have plain polynomial terms?
+    int64_t ntiles, grid;
+};
+static FewSweep few_sweep(const ttm_program* p, int k0, int k1, int64_t N, int cus) {
+    FewSweep s;
+    s.tab0 = uc(p, k0, TTM_UC_TAB_OFF);
+    s.ntab = uc(p, k1 - 1, TTM_UC_TAB_OFF) + TTM_U_TSTRIDE * uc(p, k1 - 1, TTM_UC_NI) - s.tab0;
+    if (s.ntab <= 0) { s.tab0 = 0; s.ntab = 2; }     // (no spline in the sweep - linear monotone parts: two doubles of the U section stand in)
+    s.stageable = s.ntab >= 2 && s.ntab % 2 == 0 && s.tab0 % 2 == 0 && s.ntab <= BAND_FEW_TAB;
+    s.lds = ((size_t)BAND_ET_DOUBLES + (size_t)s.ntab + 2) * 8;
+    s.lage = 1; s.plain = false;
+    for (int k = k0; k < k1; ++k)
+        for (int g = 0; g < uc(p, k, TTM_UC_N_GRP); ++g) {
+            const int32_t* G = p->h_ugrp + (uc(p, k, TTM_UC_GRP_OFF) + g) * TTM_UG_LEN;
+            const int lag = uc(p, k, TTM_UC_KC) - G[TTM_UG_VAR];
+            s.lage = lag > s.lage ? lag : s.lage;
+            s.plain = s.plain || (G[TTM_UG_FLAGS] & TTM_UGF_POLY);
+        }
+    const int64_t trows = BAND_FEW_NS * BAND_CT;
+    s.ntiles = (N + trows - 1) / trows;
+    s.grid = s.ntiles < cus ? s.ntiles : cus;
+    return s;
+}
+
+// ---- the long kernels: blocks of components whose splines are resident at a time ----
 // components per block so that the splines of a block fit `budget` bytes (0: not even one).  A sweep without any spline
-// (linear monotone parts) is one block that stages nothing.
-static int plan_blocks(const ttm_program* p, int k0, int k1, size_t budget, int* nblk_out) {
-    int worst = 0;
-    for (int k = k0; k < k1; ++k) {
-        const int b = p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI] * TTM_U_TSTRIDE * 8;
-        worst = b > worst ? b : worst;
-    }
+// (linear monotone parts) is one block that stages nothing.  `block` > 0: at most that many.
+static int plan_blocks(const ttm_program* p, int k0, int k1, size_t budget, int block) {
+    auto bytes = [&](int k) { return (size_t)uc(p, k, TTM_UC_NI) * TTM_U_TSTRIDE * 8; };
     const int ncomp = k1 - k0;
-    if (worst <= 0) { *nblk_out = 1; return ncomp; }
-    if ((size_t)worst > budget) return 0;
+    size_t worst = 0;
+    for (int k = k0; k < k1; ++k) worst = bytes(k) > worst ? bytes(k) : worst;
+    if (worst > budget) return 0;
     for (int nblk = 1; nblk <= ncomp; ++nblk) {
-        const int Bc = (ncomp + nblk - 1) / nblk;
+        const int Bc = worst == 0 ? ncomp : (ncomp + nblk - 1) / nblk;
         bool ok = true;
         for (int kb = k0; kb < k1 && ok; kb += Bc) {
             size_t s = 0;
-            for (int k = kb; k < kb + Bc && k < k1; ++k) s += (size_t)p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI] * TTM_U_TSTRIDE * 8;
+            for (int k = kb; k < kb + Bc && k < k1; ++k) s += bytes(k);
             ok = s <= budget;
         }
-        if (ok) { *nblk_out = nblk; return Bc; }
+        if (ok) return block > 0 && block < Bc ? block : Bc;
     }
     return 0;
+}
+// Dynamic LDS of the splines under a plan of Bc components per block, the largest block's.  Two rules, kept apart on purpose:
+// by SUM of the components' splines - how forward() sizes k_band_forward and k_band_density
+static size_t block_lds_sum(const ttm_program* p, int k0, int k1, int Bc) {
+    size_t lds = 0;
+    for (int kb = k0; kb < k1; kb += Bc) {
+        size_t s = 0;
+        for (int k = kb; k < kb + Bc && k < k1; ++k) s += (size_t)uc(p, k, TTM_UC_NI) * TTM_U_TSTRIDE * 8;
+        lds = s > lds ? s : lds;
+    }
+    return lds;
+}
+// by SPAN, from the block's first spline to the end of its last as they stand in the U section - what k_band_newton stages
+// (from its first component's offset, spline or not) and k_band_logdet (`splines_only`: from the first component that has one)
+static size_t block_lds_span(const ttm_program* p, int k0, int k1, int Bc, bool splines_only) {
+    size_t lds = 0;
+    for (int kb = k0; kb < k1; kb += Bc) {
+        int a = kb, b = (kb + Bc < k1 ? kb + Bc : k1) - 1;
+        if (splines_only) {
+            while (a <= b && uc(p, a, TTM_UC_NI) <= 0) ++a;
+            while (b >= a && uc(p, b, TTM_UC_NI) <= 0) --b;
+        }
+        const size_t s = a > b ? 0 : (size_t)(uc(p, b, TTM_UC_TAB_OFF) + TTM_U_TSTRIDE * uc(p, b, TTM_UC_NI) - uc(p, a, TTM_UC_TAB_OFF)) * 8;
+        lds = s > lds ? s : lds;
+    }
+    return lds;
 }
 
 int forward(const ttm_program* p, const double* U, int k0, int k1, const double* Xsoa, int64_t ldx, int64_t N, double* Zsoa, int64_t ldz,
             double* logdet, const double* sigma, double* sumsq, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name) {
+    // (rows: 2^28 here, 2^29 at the gate in ttm_kernels.hip - both stand)
     if (!usable(p, k0, k1) || (!Zsoa && !logdet && !sumsq) || N >= ((int64_t)1 << 28)) return 1;
-    const bool aligned = ((uintptr_t)Xsoa % 16 == 0) && (ldx % 2 == 0) && ldx >= ((N + 1) & ~(int64_t)1) &&
-                         (!Zsoa || ((uintptr_t)Zsoa % 16 == 0 && ldz % 2 == 0)) && ((uintptr_t)U % 16 == 0) &&
-                         (!logdet || (uintptr_t)logdet % 16 == 0) && (!sumsq || (uintptr_t)sumsq % 16 == 0);
-    if (!aligned) return 1;
-    const size_t stat = (logdet || sumsq) ? (size_t)BAND_UNI * 8 : 0;                    // (static array of the density pass)
-    if ((logdet || sumsq) && k1 - k0 > BAND_UNI) return 1;
+    // (need = 0 for Z: ldz is not held against N here, as it is in roundtrip() and newton())
+    if (!col_ok(Xsoa, ldx, even_rows(N)) || (Zsoa && !col_ok(Zsoa, ldz, 0)) || !vec_ok(U) || !vec_ok(logdet) || !vec_ok(sumsq)) return 1;
+    const bool dens = logdet || sumsq;
+    const size_t stat = dens ? (size_t)BAND_UNI * 8 : 0;                                 // (static array of the density pass)
+    if (dens && k1 - k0 > BAND_UNI) return 1;
     const size_t fixed = (size_t)BAND_ET_DOUBLES * 8 + stat;
     if (lds_per_cu <= fixed) return 1;
-    int nblk = 0;
-    int Bc = plan_blocks(p, k0, k1, lds_per_cu - fixed, &nblk);
+    const int Bc = plan_blocks(p, k0, k1, lds_per_cu - fixed, block);
     if (Bc <= 0) return 1;
-    if (block > 0 && block < Bc) Bc = block;
-    size_t lds = 0;
-    for (int kb = k0; kb < k1; kb += Bc) {
-        size_t s = 0;
-        for (int k = kb; k < kb + Bc && k < k1; ++k) s += (size_t)p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI] * TTM_U_TSTRIDE * 8;
-        lds = s > lds ? s : lds;
-    }
-    lds += fixed - stat;                                      // (dynamic part)
+    const size_t lds = block_lds_sum(p, k0, k1, Bc) + fixed - stat;                      // (dynamic part)
+    const int cls = p->u_h_cls, lag = p->u_p_lag, kcol0 = uc(p, k0, TTM_UC_KC);
     // log-determinant only: the derivative of a separable component is a function of its own column alone (k_band_logdet)
     if (logdet && !Zsoa && !sumsq && k1 - k0 <= BAND_UNI) {
         const size_t lbudget = lds_per_cu - (size_t)BAND_UNI * 8;
-        int lblk = 0;
-        int LBc = plan_blocks(p, k0, k1, lbudget, &lblk);
-        if (LBc > 0) {
-            if (block > 0 && block < LBc) LBc = block;
-            size_t llds = 16;
-            for (int kb = k0; kb < k1; kb += LBc) {
-                int tb = -1, te = 0;
-                for (int k = kb; k < kb + LBc && k < k1; ++k) {
-                    const int ni = p->h_ucomp[k * TTM_UC_LEN + TTM_UC_NI], to = p->h_ucomp[k * TTM_UC_LEN + TTM_UC_TAB_OFF];
-                    if (ni > 0) { if (tb < 0) tb = to; te = to + TTM_U_TSTRIDE * ni; }
-                }
-                const size_t sbytes = tb < 0 ? 0 : (size_t)(te - tb) * 8;
-                llds = sbytes + 16 > llds ? sbytes + 16 : llds;
-            }
-            if (llds <= lbudget) {
-                typedef void (*lkern_t)(const double*, int64_t, int, int, int, int, const double*, int64_t, int64_t, double*, const double*, int64_t, int);
-                int64_t rows = chunk_rows(N, cus);
-                const bool wide = rows >= 3 * BAND_CT;
-                lkern_t lk = p->u_p_lag == 5 ? (wide ? k_band_logdet<5, 4> : k_band_logdet<5, 2>)
-                           : p->u_p_lag == 3 ? (wide ? k_band_logdet<3, 4> : k_band_logdet<3, 2>) : (wide ? k_band_logdet<2, 4> : k_band_logdet<2, 2>);
-                const int64_t grid = (N + rows - 1) / rows;
-                allow_lds((const void*)lk, llds);
-                hipLaunchKernelGGL(lk, dim3((unsigned)grid), dim3(BAND_CT), llds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                                   (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], (int)p->u_p_stride, Xsoa, ldx, N, logdet, sigma, rows, LBc);
-                if (kernel_name) *kernel_name = "k_band_logdet";
-                return 0;
-            }
+        const int LBc = plan_blocks(p, k0, k1, lbudget, block);
+        const size_t llds = LBc > 0 ? block_lds_span(p, k0, k1, LBc, true) + 16 : 0;
+        if (LBc > 0 && llds <= lbudget) {
+            const ChunkGrid cg = chunk_grid(N, cus);
+            auto lk = with_lag(lag, [&](auto L) {
+                return with_bool(cg.rows >= 3 * BAND_CT, [&](auto wide) { return k_band_logdet<decltype(L)::value, decltype(wide)::value ? 4 : 2>; });
+            });
+            return launch(lk, cg.grid, llds, stream, "k_band_logdet", kernel_name, U, p->u_p_off, k0, k1, kcol0, p->u_p_stride, Xsoa, ldx, N, logdet,
+                          sigma, cg.rows, LBc);
         }
     }
-    const int cls = p->u_h_cls;
-    // a few components: everything requested at once, tiles of 2048 rows (k_band_few)
+    // a few components (k_band_few).  A sweep that reaches further back than its records declines outright; any other
+    // condition that fails leaves the map to the long kernels below
     if (k1 - k0 <= TTM_P_FEW_D) {
-        // the splines of the sweep as they stand in the U section (padding between them included)
-        int tab0 = p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_TAB_OFF];
-        int ntab = p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_TAB_OFF] + TTM_U_TSTRIDE * p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_NI] - tab0;
-        if (ntab <= 0) { tab0 = 0; ntab = 2; }                 // (no spline in the sweep - linear monotone parts: two doubles of the U section stand in)
-        const size_t flds = (size_t)BAND_ET_DOUBLES * 8 + ((size_t)(ntab > 0 ? ntab : 0) + 2) * 8;
-        if (ntab >= 2 && ntab % 2 == 0 && tab0 % 2 == 0 && ntab <= BAND_FEW_TAB && flds <= lds_per_cu && (!sigma || logdet)) {
-            typedef void (*fkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, int64_t, double*, int64_t, double*, const double*,
-                                    double*, int, int, int);
-            const bool dens = logdet || sumsq;
-            int lage; bool plain;
-            sweep_shape(p, k0, k1, &lage, &plain);
-            if (lage > p->u_p_lag) return 1;
-            fkern_t fk = nullptr;
-#define BAND_FEW_C(L, E, PL, DN) (cls == 1 ? k_band_few<1, L, E, PL, DN> : cls == 2 ? k_band_few<2, L, E, PL, DN> : cls == 3 ? k_band_few<3, L, E, PL, DN> : k_band_few<4, L, E, PL, DN>)
-#define BAND_FEW_P(L, E, DN) (plain ? BAND_FEW_C(L, E, true, DN) : BAND_FEW_C(L, E, false, DN))
-#define BAND_FEW_E(L, E) (dens ? BAND_FEW_P(L, E, true) : BAND_FEW_P(L, E, false))
-            if (p->u_p_lag == 5) {
-                fk = BAND_FEW_E(5, 5);                        // (records of five groups - the smoother's block map: one shape, zeros beyond a sweep's reach)
-            } else if (p->u_p_lag == 3) {
-                fk = lage == 1 ? BAND_FEW_E(3, 1) : lage == 2 ? BAND_FEW_E(3, 2) : BAND_FEW_E(3, 3);
-            } else {
-                fk = lage == 1 ? BAND_FEW_E(2, 1) : BAND_FEW_E(2, 2);
-            }
-#undef BAND_FEW_P
-#undef BAND_FEW_E
-#undef BAND_FEW_C
-            const int64_t trows = BAND_FEW_NS * BAND_CT;
-            const int64_t ntiles = (N + trows - 1) / trows;
-            const int64_t grid = ntiles < cus ? ntiles : cus;
-            allow_lds((const void*)fk, flds);
-            hipLaunchKernelGGL(fk, dim3((unsigned)grid), dim3(BAND_CT), flds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                               (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], Xsoa, ldx, N, Zsoa, ldz, logdet, sigma, sumsq, (int)ntiles, tab0, ntab);
-            if (kernel_name) *kernel_name = dens ? "k_band_few<density>" : "k_band_few";
-            return 0;
+        const FewSweep fs = few_sweep(p, k0, k1, N, cus);
+        if (fs.stageable && fs.lds <= lds_per_cu && (!sigma || logdet)) {
+            if (fs.lage > lag) return 1;
+            auto fk = with_reach(lag, fs.lage, [&](auto L, auto E) {
+                return with_bool(fs.plain, [&](auto PL) {
+                    return with_bool(dens, [&](auto DN) {
+                        return with_cls<4>(cls, [&](auto C) {
+                            return k_band_few<decltype(C)::value, decltype(L)::value, decltype(E)::value, decltype(PL)::value, decltype(DN)::value>;
+                        });
+                    });
+                });
+            });
+            return launch(fk, fs.grid, fs.lds, stream, dens ? "k_band_few<density>" : "k_band_few", kernel_name, U, p->u_p_off, k0, k1, kcol0, Xsoa,
+                          ldx, N, Zsoa, ldz, logdet, sigma, sumsq, fs.ntiles, fs.tab0, fs.ntab);
         }
     }
-    if (p->u_p_lag != 2 || cls > 3) return 1;             // (lag-3 records / order class 4: the few-component kernels only)
-    // (a map without linear own terms takes the instantiations without them: no slot [7], no test for a missing spline)
+    if (lag != 2 || cls > 3) return 1;                        // (lag-3 records / order class 4: the few-component kernels only)
     const bool own = sweep_has_own(p, k0, k1);
-    if (logdet || sumsq) {
-        typedef void (*dkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, int64_t, double*, int64_t, double*, const double*,
-                                double*, int64_t, int);
-#define BAND_DENS_K(WZ, OW) (cls == 1 ? k_band_density<1, 2, WZ, OW> : cls == 2 ? k_band_density<2, 2, WZ, OW> : k_band_density<3, 2, WZ, OW>)
-        dkern_t dk = Zsoa ? (own ? BAND_DENS_K(true, true) : BAND_DENS_K(true, false)) : (own ? BAND_DENS_K(false, true) : BAND_DENS_K(false, false));
-#undef BAND_DENS_K
-        const int64_t rows = chunk_rows(N, cus);
-        const int64_t grid = (N + rows - 1) / rows;
-        allow_lds((const void*)dk, lds);
-        hipLaunchKernelGGL(dk, dim3((unsigned)grid), dim3(BAND_CT), lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                           (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], Xsoa, ldx, N, Zsoa, ldz, logdet, sigma, sumsq, rows, Bc);
-        if (kernel_name) *kernel_name = "k_band_density";
-        return 0;
+    const ChunkGrid cg = chunk_grid(N, cus);
+    if (dens) {
+        auto dk = with_bool(Zsoa != nullptr, [&](auto WZ) {
+            return with_bool(own, [&](auto OW) {
+                return with_cls<3>(cls, [&](auto C) { return k_band_density<decltype(C)::value, 2, decltype(WZ)::value, decltype(OW)::value>; });
+            });
+        });
+        return launch(dk, cg.grid, lds, stream, "k_band_density", kernel_name, U, p->u_p_off, k0, k1, kcol0, Xsoa, ldx, N, Zsoa, ldz, logdet, sigma,
+                      sumsq, cg.rows, Bc);
     }
-    typedef void (*kern_t)(const double*, int64_t, int, int, int, const double*, int64_t, int64_t, double*, int64_t, int64_t, int);
-    kern_t kern = own ? (cls == 1 ? k_band_forward<1, 2, true> : cls == 2 ? k_band_forward<2, 2, true> : k_band_forward<3, 2, true>)
-                      : (cls == 1 ? k_band_forward<1, 2, false> : cls == 2 ? k_band_forward<2, 2, false> : k_band_forward<3, 2, false>);
-    const int64_t rows = chunk_rows(N, cus);
-    const int64_t grid = (N + rows - 1) / rows;
-    allow_lds((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BAND_CT), lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                       (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], Xsoa, ldx, N, Zsoa, ldz, rows, Bc);
-    if (kernel_name) *kernel_name = "k_band_forward";
-    return 0;
+    auto kern = with_bool(own, [&](auto OW) { return with_cls<3>(cls, [&](auto C) { return k_band_forward<decltype(C)::value, 2, decltype(OW)::value>; }); });
+    return launch(kern, cg.grid, lds, stream, "k_band_forward", kernel_name, U, p->u_p_off, k0, k1, kcol0, Xsoa, ldx, N, Zsoa, ldz, cg.rows, Bc);
 }
 
 // forward (+ density terms) + table inverse of a map of a few components in one launch (k_band_few_roundtrip); 1: not for this map /
@@ -2793,55 +2828,34 @@ int roundtrip(const ttm_program* p, const double* U, int k0, int k1, const doubl
               const double* tmin, const double* tmax, const int32_t* bkt, int nb, int cus, size_t lds_per_cu, bool force, void* stream,
               const char** kernel_name) {
     const int nc = k1 - k0;
-    if (!usable(p, k0, k1) || nc > TTM_P_FEW_D || !Xr || !y_affine || T < 64 || T + 4 > BAND_CT || nb + 1 != 1024 || N >= ((int64_t)1 << 28)) return 1;
-    if ((uintptr_t)bkt % 16 != 0 || (sigma && !logdet)) return 1;
-    const double ymax = fabs(y_affine[0]) > fabs(y_affine[2]) ? fabs(y_affine[0]) : fabs(y_affine[2]);
-    if (!(y_affine[1] > 0.0 && y_affine[1] * ymax * 0.5 <= 0.1)) return 1;
-    const int64_t need = (N + 1) & ~(int64_t)1;
-    const bool aligned = ((uintptr_t)Xsoa % 16 == 0) && (ldx % 2 == 0) && ldx >= need && (!Zsoa || ((uintptr_t)Zsoa % 16 == 0 && ldz % 2 == 0 && ldz >= need)) &&
-                         ((uintptr_t)Xr % 16 == 0) && (ldr % 2 == 0) && ldr >= need && ((uintptr_t)U % 16 == 0) &&
-                         (!logdet || (uintptr_t)logdet % 16 == 0) && (!sumsq || (uintptr_t)sumsq % 16 == 0);
-    if (!aligned) return 1;
-    int tab0 = p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_TAB_OFF];
-    int ntab = p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_TAB_OFF] + TTM_U_TSTRIDE * p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_NI] - tab0;
-    if (ntab <= 0) { tab0 = 0; ntab = 2; }
-    if (ntab < 2 || ntab % 2 != 0 || tab0 % 2 != 0 || ntab > BAND_FEW_TAB) return 1;
-    const int Weven = (T + 4 + 1) & ~1;
-    const int tab_slot = BAND_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1);
-    const size_t lds = ((size_t)nc * tab_slot + (size_t)2 * Weven + (size_t)BAND_ET_DOUBLES + (size_t)ntab + 2) * 8;
-    int lage; bool plain;
-    sweep_shape(p, k0, k1, &lage, &plain);
-    if (lds > lds_per_cu || lage > p->u_p_lag) return 1;
-    const int cls = p->u_h_cls;
+    if (!usable(p, k0, k1) || nc > TTM_P_FEW_D || !Xr || T < 64 || T + 4 > BAND_CT || nb + 1 != 1024 || N >= ((int64_t)1 << 28)) return 1;
+    if (!vec_ok(bkt) || (sigma && !logdet) || !y_affine_ok(y_affine)) return 1;
+    const int64_t need = even_rows(N);
+    if (!col_ok(Xsoa, ldx, need) || (Zsoa && !col_ok(Zsoa, ldz, need)) || !col_ok(Xr, ldr, need) || !vec_ok(U) || !vec_ok(logdet) || !vec_ok(sumsq))
+        return 1;
+    const FewSweep fs = few_sweep(p, k0, k1, N, cus);
+    const BandImageSlot slot = band_image_slot(T, nb);
+    const size_t lds = slot.lds(nc) + fs.lds;
+    if (!fs.stageable || lds > lds_per_cu || fs.lage > p->u_p_lag) return 1;
     const bool dens = logdet || sumsq;
     // Where it pays (measured, graph replay): sweeps that reach one or two columns back, without the density terms - C2b 19.9 us
     // against 10.1 + 11.8 us.  A reach of three columns (C3: 29.8 against 10.5 + 13.1 us) and the density variant (C2b 31.6
     // against 15.9 + 11.8 us) run out of registers (34-117 spilled with the inverse sweep's 128 in use): the launches are bound by the
     // latency of a row's chain of dependent operations, not by the columns' traffic, so one pass instead of two saves a launch
     // floor and a round trip, not the arithmetic.  `force`: tests (every shape through the fused kernel).
-    if (!force && (lage > 2 || dens)) return 1;
-    typedef void (*rkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, int64_t, double*, int64_t, double*, int64_t, double*,
-                            const double*, double*, const double*, int, double, double, double, const double*, const double*, const int*, int, int, int,
-                            int, int);
-    rkern_t rk = nullptr;
-#define BAND_RTF_C(L, E, PL, DN) (cls == 1 ? k_band_few_roundtrip<1, L, E, PL, DN> : cls == 2 ? k_band_few_roundtrip<2, L, E, PL, DN> : cls == 3 ? k_band_few_roundtrip<3, L, E, PL, DN> : k_band_few_roundtrip<4, L, E, PL, DN>)
-#define BAND_RTF_P(L, E, DN) (plain ? BAND_RTF_C(L, E, true, DN) : BAND_RTF_C(L, E, false, DN))
-#define BAND_RTF_E(L, E) (dens ? BAND_RTF_P(L, E, true) : BAND_RTF_P(L, E, false))
-    if (p->u_p_lag == 5) rk = BAND_RTF_E(5, 5);
-    else if (p->u_p_lag == 3) rk = lage == 1 ? BAND_RTF_E(3, 1) : lage == 2 ? BAND_RTF_E(3, 2) : BAND_RTF_E(3, 3);
-    else rk = lage == 1 ? BAND_RTF_E(2, 1) : BAND_RTF_E(2, 2);
-#undef BAND_RTF_E
-#undef BAND_RTF_P
-#undef BAND_RTF_C
-    const int64_t trows = BAND_FEW_NS * BAND_CT;
-    const int64_t ntiles = (N + trows - 1) / trows;
-    const int64_t grid = ntiles < cus ? ntiles : cus;
-    allow_lds((const void*)rk, lds);
-    hipLaunchKernelGGL(rk, dim3((unsigned)grid), dim3(BAND_CT), lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                       (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], Xsoa, ldx, N, Zsoa, ldz, Xr, ldr, logdet, sigma, sumsq, tab_x, T, y_affine[0],
-                       y_affine[1], y_affine[2], tmin, tmax, bkt, nb, tab_slot, (int)ntiles, tab0, ntab);
-    if (kernel_name) *kernel_name = dens ? "k_band_few_roundtrip<density>" : "k_band_few_roundtrip";
-    return 0;
+    if (!force && (fs.lage > 2 || dens)) return 1;
+    auto rk = with_reach(p->u_p_lag, fs.lage, [&](auto L, auto E) {
+        return with_bool(fs.plain, [&](auto PL) {
+            return with_bool(dens, [&](auto DN) {
+                return with_cls<4>(p->u_h_cls, [&](auto C) {
+                    return k_band_few_roundtrip<decltype(C)::value, decltype(L)::value, decltype(E)::value, decltype(PL)::value, decltype(DN)::value>;
+                });
+            });
+        });
+    });
+    return launch(rk, fs.grid, lds, stream, dens ? "k_band_few_roundtrip<density>" : "k_band_few_roundtrip", kernel_name, U, p->u_p_off, k0, k1,
+                  uc(p, k0, TTM_UC_KC), Xsoa, ldx, N, Zsoa, ldz, Xr, ldr, logdet, sigma, sumsq, tab_x, T, y_affine[0], y_affine[1], y_affine[2], tmin,
+                  tmax, bkt, nb, slot.tab_slot, fs.ntiles, fs.tab0, fs.ntab);
 }
 
 // Newton root search in push form (k_band_few_newton / k_band_newton); 1: not for this map / these buffers (the caller
@@ -2849,62 +2863,29 @@ int roundtrip(const ttm_program* p, const double* U, int k0, int k1, const doubl
 int newton(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
            int32_t* iters, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name) {
     if (!usable(p, k0, k1) || !iters || N < 1 || N >= ((int64_t)1 << 28) || cus < 1) return 1;
-    const int64_t need = (N + 1) & ~(int64_t)1;
-    const bool aligned = ((uintptr_t)Zsoa % 16 == 0) && (ldz % 2 == 0) && ldz >= need && ((uintptr_t)Xsoa % 16 == 0) && (ldx % 2 == 0) &&
-                         ldx >= need && ((uintptr_t)U % 16 == 0);
-    if (!aligned) return 1;
-    const int cls = p->u_h_cls, lag = p->u_p_lag, kcol0 = p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC];
+    if (!col_ok(Zsoa, ldz, even_rows(N)) || !col_ok(Xsoa, ldx, even_rows(N)) || !vec_ok(U)) return 1;
+    const int cls = p->u_h_cls, lag = p->u_p_lag, kcol0 = uc(p, k0, TTM_UC_KC);
     if (k1 - k0 <= TTM_P_FEW_D) {
-        // the splines of the sweep as they stand in the U section (padding between them included)
-        int tab0 = p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_TAB_OFF];
-        int ntab = p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_TAB_OFF] + TTM_U_TSTRIDE * p->h_ucomp[(k1 - 1) * TTM_UC_LEN + TTM_UC_NI] - tab0;
-        if (ntab <= 0) { tab0 = 0; ntab = 2; }                 // (no spline in the sweep - linear monotone parts: two doubles of the U section stand in)
-        const size_t flds = (size_t)BAND_ET_DOUBLES * 8 + ((size_t)ntab + 2) * 8;
-        int lage; bool plain;
-        sweep_shape(p, k0, k1, &lage, &plain);
-        if (ntab >= 2 && ntab % 2 == 0 && tab0 % 2 == 0 && ntab <= BAND_FEW_TAB && flds <= lds_per_cu && lage <= lag) {
-            typedef void (*fkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, double*, int64_t, int64_t, int*, int, int, int);
-#define BAND_FEWN_C(L) (cls == 1 ? k_band_few_newton<1, L> : cls == 2 ? k_band_few_newton<2, L> : cls == 3 ? k_band_few_newton<3, L> : k_band_few_newton<4, L>)
-            fkern_t fk = lag == 5 ? BAND_FEWN_C(5) : lag == 3 ? BAND_FEWN_C(3) : BAND_FEWN_C(2);
-#undef BAND_FEWN_C
-            const int64_t trows = BAND_FEW_NS * BAND_CT;
-            const int64_t ntiles = (N + trows - 1) / trows;
-            const int64_t grid = ntiles < cus ? ntiles : cus;
-            allow_lds((const void*)fk, flds);
-            hipLaunchKernelGGL(fk, dim3((unsigned)grid), dim3(BAND_CT), flds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1, kcol0, Zsoa, ldz,
-                               Xsoa, ldx, N, (int*)iters, (int)ntiles, tab0, ntab);
-            if (kernel_name) *kernel_name = "k_band_few_newton";
-            return 0;
+        const FewSweep fs = few_sweep(p, k0, k1, N, cus);
+        // (a sweep that reaches further back than its records falls through to the checks of the long kernel; it does not return)
+        if (fs.stageable && fs.lds <= lds_per_cu && fs.lage <= lag) {
+            auto fk = with_lag(lag, [&](auto L) { return with_cls<4>(cls, [&](auto C) { return k_band_few_newton<decltype(C)::value, decltype(L)::value>; }); });
+            return launch(fk, fs.grid, fs.lds, stream, "k_band_few_newton", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, iters,
+                          fs.ntiles, fs.tab0, fs.ntab);
         }
     }
     if (lag != 2 || cls > 3) return 1;                        // (lag-3 records / order class 4: the few-component kernel only)
     const size_t fixed = (size_t)BAND_ET_DOUBLES * 8;
     if (lds_per_cu <= fixed) return 1;
-    int nblk = 0;
-    int Bc = plan_blocks(p, k0, k1, lds_per_cu - fixed, &nblk);         // (the residency plan of forward())
+    const int Bc = plan_blocks(p, k0, k1, lds_per_cu - fixed, block);                    // (the residency plan of forward())
     if (Bc <= 0) return 1;
-    if (block > 0 && block < Bc) Bc = block;
-    size_t lds = 0;
-    for (int kb = k0; kb < k1; kb += Bc) {
-        const int ke = kb + Bc < k1 ? kb + Bc : k1;
-        // (what the kernel stages: from the block's first spline to the end of its last)
-        const size_t s = (size_t)(p->h_ucomp[(ke - 1) * TTM_UC_LEN + TTM_UC_TAB_OFF] + TTM_U_TSTRIDE * p->h_ucomp[(ke - 1) * TTM_UC_LEN + TTM_UC_NI] -
-                                  p->h_ucomp[kb * TTM_UC_LEN + TTM_UC_TAB_OFF]) * 8;
-        lds = s > lds ? s : lds;
-    }
-    lds += fixed;
+    const size_t lds = block_lds_span(p, k0, k1, Bc, false) + fixed;
     if (lds > lds_per_cu) return 1;
-    typedef void (*kern_t)(const double*, int64_t, int, int, int, const double*, int64_t, double*, int64_t, int64_t, int*, int64_t, int);
-    // (a map without linear own terms takes the instantiations without them)
-    kern_t kern = sweep_has_own(p, k0, k1) ? (cls == 1 ? k_band_newton<1, 2, true> : cls == 2 ? k_band_newton<2, 2, true> : k_band_newton<3, 2, true>)
-                                           : (cls == 1 ? k_band_newton<1, 2, false> : cls == 2 ? k_band_newton<2, 2, false> : k_band_newton<3, 2, false>);
-    const int64_t rows = chunk_rows(N, cus);
-    const int64_t grid = (N + rows - 1) / rows;
-    allow_lds((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BAND_CT), lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa,
-                       ldx, N, (int*)iters, rows, Bc);
-    if (kernel_name) *kernel_name = "k_band_newton";
-    return 0;
+    const ChunkGrid cg = chunk_grid(N, cus);
+    auto kern = with_bool(sweep_has_own(p, k0, k1), [&](auto OW) {
+        return with_cls<3>(cls, [&](auto C) { return k_band_newton<decltype(C)::value, 2, decltype(OW)::value>; });
+    });
+    return launch(kern, cg.grid, lds, stream, "k_band_newton", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, iters, cg.rows, Bc);
 }
 
 constexpr double BAND_WFRAC = 0.52;                  /* fraction of a table's grid points a window keeps (k_inverse_rt) */
@@ -2918,105 +2899,71 @@ bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, size_t lds_
     return true;
 }
 
+// k_band_inverse: whole blocks of Bc tables [w0, w0 + W) resident at a time (+ a short block: the kernel staggers them); Bc = 0: none fits
+struct BlockPlan { int W, w0, tab_slot, Bc, nblk; size_t lds; };
+static BlockPlan block_plan(int T, int W, int nb, int ncomp, size_t lds_per_cu, int block) {
+    const BandImageSlot slot = band_image_slot(W, nb);
+    BlockPlan b = {W, (T - W) / 2, slot.tab_slot, 0, 0, 0};
+    if (slot.lds(1) > lds_per_cu) return b;
+    b.Bc = (int)((lds_per_cu - slot.lds(0)) / ((size_t)slot.tab_slot * 8));
+    if (b.Bc > ncomp) b.Bc = ncomp;
+    if (b.Bc > BAND_RT_KMAX) b.Bc = BAND_RT_KMAX;
+    if (block > 0 && block < b.Bc) b.Bc = block;
+    b.nblk = (ncomp + b.Bc - 1) / b.Bc;
+    b.lds = slot.lds(b.Bc);
+    return b;
+}
+
+// table inverse, in this order: the few-component kernel, the ring kernel (images at hand, laid out for this very plan), the block kernel
 int inverse(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
             const double* tab_x, int T, const double* y_affine, const double* tmin, const double* tmax, const int32_t* bkt, int nb, const double* img,
             int img_doubles, int cus, size_t lds_per_cu, int window, int block, void* stream, const char** kernel_name) {
-    if (!usable(p, k0, k1) || !y_affine || T < 64 || T > 4096 || nb + 1 != 1024 || N >= ((int64_t)1 << 28)) return 1;      // (bucket rows copied 16 bytes at a time, 256 units per row)
-    if ((uintptr_t)bkt % 16 != 0) return 1;
-    const double ymax = fabs(y_affine[0]) > fabs(y_affine[2]) ? fabs(y_affine[0]) : fabs(y_affine[2]);
-    if (!(y_affine[1] > 0.0 && y_affine[1] * ymax * 0.5 <= 0.1)) return 1;                 // (exp(w) by its Taylor polynomial)
-    const bool aligned = ((uintptr_t)Zsoa % 16 == 0) && (ldz % 2 == 0) && ldz >= ((N + 1) & ~(int64_t)1) && ((uintptr_t)Xsoa % 16 == 0) &&
-                         (ldx % 2 == 0) && ldx >= ((N + 1) & ~(int64_t)1);
-    if (!aligned) return 1;
-    const int ncomp = k1 - k0;
+    if (!usable(p, k0, k1) || T < 64 || T > 4096 || nb + 1 != 1024 || N >= ((int64_t)1 << 28)) return 1;      // (bucket rows copied 16 bytes at a time, 256 units per row)
+    if (!vec_ok(bkt) || !y_affine_ok(y_affine)) return 1;
+    if (!col_ok(Zsoa, ldz, even_rows(N)) || !col_ok(Xsoa, ldx, even_rows(N))) return 1;
+    const int ncomp = k1 - k0, cls = p->u_h_cls, lag = p->u_p_lag, kcol0 = uc(p, k0, TTM_UC_KC);
     // a few components: whole tables, everything requested at once, tiles of 2048 rows
     if (ncomp <= TTM_P_FEW_D && T + 4 <= BAND_CT && window <= 0) {          // (no blocks, no windows: `block` does not apply)
-        const int Weven = (T + 4 + 1) & ~1;
-        const int tab_slot = BAND_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1);
-        const size_t lds = ((size_t)ncomp * tab_slot + (size_t)2 * Weven) * 8;
-        int lage; bool plain;
-        sweep_shape(p, k0, k1, &lage, &plain);
-        if (lds <= lds_per_cu && lage <= p->u_p_lag) {
-            typedef void (*fkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, double*, int64_t, int64_t, const double*, int,
-                                    double, double, double, const double*, const double*, const int*, int, int, int);
-            const int cls = p->u_h_cls;
-            fkern_t fk = nullptr;
-#define BAND_FEWI_C(L, E, PL) (cls == 1 ? k_band_few_inverse<1, L, E, PL> : cls == 2 ? k_band_few_inverse<2, L, E, PL> : cls == 3 ? k_band_few_inverse<3, L, E, PL> : k_band_few_inverse<4, L, E, PL>)
-#define BAND_FEWI_E(L, E) (plain ? BAND_FEWI_C(L, E, true) : BAND_FEWI_C(L, E, false))
-            if (p->u_p_lag == 5) fk = BAND_FEWI_E(5, 5);
-            else if (p->u_p_lag == 3) fk = lage == 1 ? BAND_FEWI_E(3, 1) : lage == 2 ? BAND_FEWI_E(3, 2) : BAND_FEWI_E(3, 3);
-            else fk = lage == 1 ? BAND_FEWI_E(2, 1) : BAND_FEWI_E(2, 2);
-#undef BAND_FEWI_E
-#undef BAND_FEWI_C
-            const int64_t ntiles = (N + BAND_FEW_NS * BAND_CT - 1) / (BAND_FEW_NS * BAND_CT);
-            const int64_t grid = ntiles < cus ? ntiles : cus;
-            allow_lds((const void*)fk, lds);
-            hipLaunchKernelGGL(fk, dim3((unsigned)grid), dim3(BAND_CT), lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                               (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], Zsoa, ldz, Xsoa, ldx, N, tab_x, T, y_affine[0], y_affine[1], y_affine[2],
-                               tmin, tmax, bkt, nb, tab_slot, (int)ntiles);
-            if (kernel_name) *kernel_name = "k_band_few_inverse";
-            return 0;
+        const BandImageSlot slot = band_image_slot(T, nb);
+        const FewSweep fs = few_sweep(p, k0, k1, N, cus);
+        // (a sweep that reaches further back than its records falls through to the checks below; it does not return)
+        if (slot.lds(ncomp) <= lds_per_cu && fs.lage <= lag) {
+            auto fk = with_reach(lag, fs.lage, [&](auto L, auto E) {
+                return with_bool(fs.plain, [&](auto PL) {
+                    return with_cls<4>(cls, [&](auto C) {
+                        return k_band_few_inverse<decltype(C)::value, decltype(L)::value, decltype(E)::value, decltype(PL)::value>;
+                    });
+                });
+            });
+            return launch(fk, fs.grid, slot.lds(ncomp), stream, "k_band_few_inverse", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx,
+                          N, tab_x, T, y_affine[0], y_affine[1], y_affine[2], tmin, tmax, bkt, nb, slot.tab_slot, fs.ntiles);
         }
     }
-    if (p->u_p_lag != 2 || p->u_h_cls > 3) return 1;       // (lag-3 records / order class 4: the few-component kernels only)
+    if (lag != 2 || cls > 3) return 1;                        // (lag-3 records / order class 4: the few-component kernels only)
+    const ChunkGrid cg = chunk_grid(N, cus);
     // resident-table images at hand (ttm_inverse_table_build_index wrote them): the ring kernel
     BandRingPlan pl;
-    if (img && (uintptr_t)img % 16 == 0 && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl) &&
+    if (img && vec_ok(img) && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl) &&
         pl.tab_slot == img_doubles) {                         // (laid out for another plan - options changed in between: not this kernel)
-        typedef void (*rkern_t)(const double*, int64_t, int, int, int, const double*, int64_t, double*, int64_t, int64_t, const double*, int, double,
-                                double, double, const double*, const double*, const double*, int, int, int, int64_t, int, int);
-        const int cls = p->u_h_cls;
-#define BAND_RING_K(G) (cls == 1 ? k_band_inverse_ring<1, 2, G> : cls == 2 ? k_band_inverse_ring<2, 2, G> : k_band_inverse_ring<3, 2, G>)
-        rkern_t rk = pl.G == 4 ? BAND_RING_K(4) : BAND_RING_K(0);
-#undef BAND_RING_K
-        const int64_t rows = chunk_rows(N, cus);
-        const int64_t grid = (N + rows - 1) / rows;
-        allow_lds((const void*)rk, pl.lds);
-        hipLaunchKernelGGL(rk, dim3((unsigned)grid), dim3(BAND_CT), pl.lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                           (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], Zsoa, ldz, Xsoa, ldx, N, tab_x, T, y_affine[0], y_affine[1], y_affine[2], tmin,
-                           tmax, img, nb, pl.tab_slot, pl.R, rows, pl.w0, pl.W);
-        if (kernel_name) *kernel_name = "k_band_inverse_ring";
-        return 0;
+        auto rk = with_bool(pl.G == 4, [&](auto G4) {
+            return with_cls<3>(cls, [&](auto C) { return k_band_inverse_ring<decltype(C)::value, 2, decltype(G4)::value ? 4 : 0>; });
+        });
+        return launch(rk, cg.grid, pl.lds, stream, "k_band_inverse_ring", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, tab_x, T,
+                      y_affine[0], y_affine[1], y_affine[2], tmin, tmax, img, nb, pl.tab_slot, pl.R, cg.rows, pl.w0, pl.W);
     }
-    int W = T, w0 = 0, Weven = 0, tab_slot = 0, Bc = 0, nblk = 0;
-    size_t lds = 0;
-    auto plan = [&]() {
-        Weven = (W + 4 + 1) & ~1;
-        tab_slot = BAND_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1);
-        const size_t fixed = (size_t)2 * Weven * 8;
-        Bc = 0;
-        if (fixed + (size_t)tab_slot * 8 > lds_per_cu) return;
-        Bc = (int)((lds_per_cu - fixed) / ((size_t)tab_slot * 8));
-        if (Bc > ncomp) Bc = ncomp;
-        if (Bc > BAND_RT_KMAX) Bc = BAND_RT_KMAX;
-        if (block > 0 && block < Bc) Bc = block;
-        nblk = (ncomp + Bc - 1) / Bc;                                     // (full blocks + a short one: k_band_inverse staggers them)
-        lds = fixed + (size_t)Bc * tab_slot * 8;
-    };
-    plan();
-    // windowed tables when that saves a pass over the chunk (k_inverse_rt)
-    if (window != 0 && (window > 0 || (Bc > 0 && nblk > 1))) {
-        const int Bfull = Bc, nfull = nblk;
-        W = window > 0 ? (window < 16 ? 16 : window) : (int)(BAND_WFRAC * T);
+    BlockPlan b = block_plan(T, T, nb, ncomp, lds_per_cu, block);
+    // windowed tables when that saves a pass over the chunk (k_inverse_rt): on request (window > 0: whenever they fit), or by
+    // default (window < 0) when whole tables need several blocks and windowed ones fewer
+    if (window != 0 && (window > 0 || (b.Bc > 0 && b.nblk > 1))) {
+        int W = window > 0 ? (window < 16 ? 16 : window) : (int)(BAND_WFRAC * T);
         if (W >= T) W = T - 1;
-        w0 = (T - W) / 2;
-        plan();
-        if (Bc == 0 || (window < 0 && !(Bfull > 0 && nblk < nfull))) { W = T; w0 = 0; plan(); }
+        const BlockPlan w = block_plan(T, W, nb, ncomp, lds_per_cu, block);
+        if (w.Bc > 0 && (window > 0 || w.nblk < b.nblk)) b = w;
     }
-    if (Bc <= 0) return 1;
-    typedef void (*kern_t)(const double*, int64_t, int, int, int, const double*, int64_t, double*, int64_t, int64_t, const double*, int, double,
-                           double, double, const double*, const double*, const int*, int, int, int, int64_t, int, int);
-    const int cls = p->u_h_cls;
-    kern_t kern;
-    kern = cls == 1 ? k_band_inverse<1, 2, BAND_RT_KMAX> : cls == 2 ? k_band_inverse<2, 2, BAND_RT_KMAX> : k_band_inverse<3, 2, BAND_RT_KMAX>;
-    const int64_t rows = chunk_rows(N, cus);
-    const int64_t grid = (N + rows - 1) / rows;
-    allow_lds((const void*)kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BAND_CT), lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, k0, k1,
-                       (int)p->h_ucomp[k0 * TTM_UC_LEN + TTM_UC_KC], Zsoa, ldz, Xsoa, ldx, N, tab_x, T, y_affine[0], y_affine[1], y_affine[2], tmin,
-                       tmax, bkt, nb, tab_slot, Bc, rows, w0, W);
-    if (kernel_name) *kernel_name = "k_band_inverse";
-    return 0;
+    if (b.Bc <= 0) return 1;
+    auto kern = with_cls<3>(cls, [&](auto C) { return k_band_inverse<decltype(C)::value, 2, BAND_RT_KMAX>; });
+    return launch(kern, cg.grid, b.lds, stream, "k_band_inverse", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, tab_x, T,
+                  y_affine[0], y_affine[1], y_affine[2], tmin, tmax, bkt, nb, b.tab_slot, b.Bc, cg.rows, b.w0, b.W);
 }
 
 }  // namespace ttm_band

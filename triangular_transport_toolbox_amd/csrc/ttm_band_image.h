@@ -18,6 +18,17 @@
 #define BAND_RT_HDR 6
 #define BAND_RING_KMAX 24                             /* slots of the ring, at most */
 
+// doubles of one image: header, the window's entries up to an even count, the bucket index (four uint16 per double, even).
+// THE one copy of this geometry: the kernel that writes the images and every kernel that reads them take it from here.
+struct BandImageSlot {
+    int Weven, tab_slot;
+    size_t lds(int slots) const { return ((size_t)2 * Weven + (size_t)slots * tab_slot) * 8; }   // `slots` images next to the {E_i, y_i} pairs of the window
+};
+static inline BandImageSlot band_image_slot(int W, int nb) {
+    const int Weven = (W + 4 + 1) & ~1;
+    return {Weven, BAND_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1)};
+}
+
 struct BandRingPlan {
     int W, w0, Weven, tab_slot;                       // window [w0, w0 + W) of every table, doubles per image
     int R, G;                                         // ring of R slots, refilled G at a time (G = 0: every component resident, no refill)
@@ -29,11 +40,9 @@ struct BandRingPlan {
 static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, int window, int block, double wfrac, BandRingPlan* pl) {
     if (T < 64 || T > 4096 || nb + 1 != 1024 || ncomp < 1) return false;
     auto fit = [&](int W) {                           // slots that fit next to the {E_i, y_i} pairs of the window
-        const int Weven = (W + 4 + 1) & ~1;
-        const int tab_slot = BAND_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1);
-        const size_t fixed = (size_t)2 * Weven * 8;
-        if (fixed + (size_t)tab_slot * 8 > lds_per_cu) return 0;
-        int B = (int)((lds_per_cu - fixed) / ((size_t)tab_slot * 8));
+        const BandImageSlot s = band_image_slot(W, nb);
+        if (s.lds(1) > lds_per_cu) return 0;
+        int B = (int)((lds_per_cu - s.lds(0)) / ((size_t)s.tab_slot * 8));
         if (B > BAND_RING_KMAX) B = BAND_RING_KMAX;
         if (block > 0 && block < B) B = block;
         return B;
@@ -49,8 +58,8 @@ static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, i
     }
     if (B <= 0) return false;
     pl->W = W; pl->w0 = w0;
-    pl->Weven = (W + 4 + 1) & ~1;
-    pl->tab_slot = BAND_RT_HDR + pl->Weven + (((nb + 1 + 3) / 4 + 1) & ~1);
+    const BandImageSlot slot = band_image_slot(W, nb);
+    pl->Weven = slot.Weven; pl->tab_slot = slot.tab_slot;
     if (pl->tab_slot % 2) return false;               // (16-byte units)
     if (ncomp <= B) { pl->R = ncomp; pl->G = 0; }
     else {
@@ -59,7 +68,7 @@ static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, i
         if (R < 3 * G) return false;                  // (a refill is certified one group after it is issued and used two groups on)
         pl->R = R; pl->G = G;
     }
-    pl->lds = (size_t)2 * pl->Weven * 8 + (size_t)pl->R * pl->tab_slot * 8;
+    pl->lds = slot.lds(pl->R);
     return true;
 }
 
