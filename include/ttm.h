@@ -22,7 +22,10 @@
  *    ttm_last_error_string() describes the last failure of the calling thread;
  *    no exception crosses the boundary;
  *  - sample matrices are column-major on the device ("SoA": column j of an
- *    N-sample ensemble starts at X + j*ldx, ldx >= N), fp64 throughout;
+ *    N-sample ensemble starts at X + j*ldx, ldx >= N), fp64 throughout; an entry
+ *    point writes rows [0, N) of its output columns and vectors and nothing else,
+ *    and no result depends on rows [N, ldx) of an input
+ *    (tests/test_row_ownership.py);
  *  - handles do not exist: a map is described by a `ttm_program` value (plain
  *    struct of sizes, small host tables and device table pointers) compiled by
  *    the host from the reference's `monotone` / `nonmonotone` lists.
