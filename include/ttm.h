@@ -677,6 +677,37 @@ int ttm_stream_synchronize(void* stream);
 /* ttm_signal: *flag = value, ordered behind everything already enqueued on the stream.  With flag in pinned host memory
  * a host loop polls it instead of paying hipStreamSynchronize per objective evaluation (ttm_optimize_separable does). */
 int ttm_signal(double* flag, double value, void* stream);
+
+/* ---- TEST HOOK (not part of the map path): the fp64 primitives of the kernels, one element per thread -------------
+ * ttm_math_probe: out[i] = f(a[i]) or f(a[i], b[i]), i < n, for the DEVICE build of the primitive `which` - the tables
+ * staged and the coefficient pointers obtained exactly as the map kernels do it (erf table and 2^(j/32) table in LDS,
+ * series coefficients from constant memory, the band kernels' pair table through their own loader).  a, b, out: device,
+ * n doubles; b only for the two-operand ids (NULL otherwise).  The *_V2 ids evaluate the VecD<2> form: element i pairs
+ * with element i + 1 (the last element of an odd n pairs with itself inside the kernel; the buffers hold n doubles).
+ * TTM_PROBE_DENSE_EXP_CORE has no guards: |a[i]| <= 800, no NaN.
+ * TTM_E_ARG: unknown id, n < 0, a null pointer, b missing for a two-operand id - nothing is launched; n = 0: no-op.
+ * The host test double serves the ids whose host build runs the same algorithm (0..7, 10..12) and returns
+ * TTM_E_UNSUPPORTED for the others (reciprocal start values and the primitives private to csrc/ttm_band.hip).      */
+#define TTM_PROBE_FAST_EXP 0
+#define TTM_PROBE_ERF_TAB 1             /* erf_gauss_tab<true>: the erf output */
+#define TTM_PROBE_GAUSS_TAB 2           /* erf_gauss_tab<true>: the exp(-t^2) output */
+#define TTM_PROBE_FAST_LOG 3
+#define TTM_PROBE_FAST_RCP 4
+#define TTM_PROBE_FAST_DIV 5            /* a / b */
+#define TTM_PROBE_EXP_Q_TAB 6
+#define TTM_PROBE_EXP_Q_FAST 7
+#define TTM_PROBE_FAST_DIV1 8           /* a / b */
+#define TTM_PROBE_APPROX_RCP 9
+#define TTM_PROBE_DENSE_EXP_CORE 10
+#define TTM_PROBE_FAST_EXP_V2 11
+#define TTM_PROBE_EXP_Q_FAST_V2 12
+#define TTM_PROBE_BAND_EXPQ 32
+#define TTM_PROBE_BAND_EXPQ_SERIES 33
+#define TTM_PROBE_BAND_EXPQ_FAR 34
+#define TTM_PROBE_BAND_LOG 35
+#define TTM_PROBE_BAND_DIV 36           /* a / b */
+int ttm_math_probe(int32_t which, const double* a, const double* b, int64_t n, double* out, void* stream);
+
 typedef int32_t (*ttm_objective_cb)(int32_t n, const double* x, double* f, double* g, void* user);
 int ttm_lbfgsb_minimize(int32_t n, double* x, const double* lb, const double* ub, ttm_objective_cb fun, void* user,
                         int32_t maxiter, double* result);

@@ -55,7 +55,7 @@ def lib():
     global _lib
     if _lib is None:
         l = ctypes.CDLL(build())
-        for name, (res, args) in _capi._SIGNATURES.items():
+        for name, (res, args) in list(_capi._SIGNATURES.items()) + list(_capi._TEST_HOOK_SIGNATURES.items()):
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         # the collective: performed by torch.distributed (gloo) on the host buffer the double hands over

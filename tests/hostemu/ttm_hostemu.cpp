@@ -619,6 +619,31 @@ int emu_math(int which, const double* a, const double* b, int64_t n, double* out
     return 0;
 }
 
+// the test hook of include/ttm.h on the HOST build of the primitives: the ids of emu_math forward to it; dense_exp_core and
+// the VecD<2> forms run the same source as the device; the reciprocal start value, fast_div1 (plain divisions in the host
+// build) and the primitives private to csrc/ttm_band.hip have no host counterpart
+int ttm_math_probe(int32_t which, const double* a, const double* b, int64_t n, double* out, void*) {
+    const bool band = which >= TTM_PROBE_BAND_EXPQ && which <= TTM_PROBE_BAND_DIV;
+    if (!band && (which < TTM_PROBE_FAST_EXP || which > TTM_PROBE_EXP_Q_FAST_V2)) return TTM_E_ARG;
+    const bool two = which == TTM_PROBE_FAST_DIV || which == TTM_PROBE_FAST_DIV1 || which == TTM_PROBE_BAND_DIV;
+    if (n < 0 || !a || !out || (two && !b)) return TTM_E_ARG;
+    if (band || which == TTM_PROBE_FAST_DIV1 || which == TTM_PROBE_APPROX_RCP) return TTM_E_UNSUPPORTED;
+    if (which <= TTM_PROBE_EXP_Q_FAST) return emu_math(which, a, b, n, out);
+    if (which == TTM_PROBE_DENSE_EXP_CORE) {
+        for (int64_t i = 0; i < n; ++i) out[i] = dense_exp_core(a[i]);
+        return TTM_OK;
+    }
+    for (int64_t i = 0; i < n; i += 2) {
+        const int64_t i1 = i + 1 < n ? i + 1 : i;
+        VecD<2> x;
+        x.v[0] = a[i]; x.v[1] = a[i1];
+        const VecD<2> r = which == TTM_PROBE_FAST_EXP_V2 ? fast_exp(x) : exp_q_fast(x);
+        out[i] = r.v[0];
+        if (i1 != i) out[i1] = r.v[1];
+    }
+    return TTM_OK;
+}
+
 int ttm_basis(const ttm_program* p, int32_t k, int32_t which, const double* X, int64_t ldx, int64_t N, double* out, int64_t ldo, void*) {
     const Prog g = make_prog(p);
     HostComp h;

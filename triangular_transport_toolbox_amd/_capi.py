@@ -122,7 +122,13 @@ _SIGNATURES = {
     'ttm_allreduce_i32': (ctypes.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),
 }
 
-EXPORTED_SYMBOLS = sorted(_SIGNATURES)
+# test hooks of include/ttm.h: exported and typed like the rest, but kept apart from the map path's table - whoever walks
+# _SIGNATURES over a library (the host test double of the suite does) needs only the map path to be there
+_TEST_HOOK_SIGNATURES = {
+    'ttm_math_probe': (ctypes.c_int, [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),
+}
+
+EXPORTED_SYMBOLS = sorted(set(_SIGNATURES) | set(_TEST_HOOK_SIGNATURES))
 
 _lib = None
 
@@ -149,7 +155,7 @@ def load():
         # cannot share streams / allocations (and the second one finds no GPU).
         import torch  # noqa: F401
         lib = ctypes.CDLL(path)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_TEST_HOOK_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.ttm_program_sizeof() != ctypes.sizeof(ttm_program):

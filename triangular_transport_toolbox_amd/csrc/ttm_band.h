@@ -60,4 +60,9 @@ int roundtrip(const ttm_program* p, const double* U, int k0, int k1, const doubl
 // [w0, w0 + W) of every table and the doubles per image (the table-building kernel writes them, `inverse` reads them)
 bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, size_t lds_per_cu, int window, int block, int* w0, int* W, int* tab_slot);
 
+// TEST HOOK (ttm_math_probe, include/ttm.h): out[i] = f(a[i] [, b[i]]) for the primitives private to csrc/ttm_band.hip -
+// `which` one of TTM_PROBE_BAND_* (the caller has checked it and the pointers; n >= 1).  The pair table is staged by the
+// forward kernels' loader, the Taylor coefficients are g_band_taylor.
+int math_probe(int which, const double* a, const double* b, int64_t n, double* out, void* stream, const char** kernel_name);
+
 }  // namespace ttm_band

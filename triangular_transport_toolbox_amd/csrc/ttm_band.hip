@@ -2579,6 +2579,31 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_newton(const double* __res
 }
 
 // ---------------------------------------------------------------------------
+// TEST HOOK (ttm_math_probe, include/ttm.h): the primitives of this file on arrays, one element per thread - the pair table
+// staged by the loader of k_band_forward, the Taylor coefficients read as the kernels read them.  No map kernel calls this.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(BAND_CT) void k_band_math_probe(int which, const double* __restrict__ a, const double* __restrict__ b,
+                                                             int64_t n, double* __restrict__ out) {
+    extern __shared__ __align__(16) double g_lds[];
+    double* etab = g_lds;
+    band_stage(etab, g_band_etab, 2 * TTM_BAND_ET_N);
+    __syncthreads();
+    cdbl_p kt = (cdbl_p)g_band_taylor;
+    const int64_t i = (int64_t)blockIdx.x * BAND_CT + threadIdx.x;
+    if (i >= n) return;
+    const double x = a[i];
+    double r;
+    switch (which) {
+        case TTM_PROBE_BAND_EXPQ: r = band_expq(etab, x, kt); break;
+        case TTM_PROBE_BAND_EXPQ_SERIES: r = band_expq_series(x); break;
+        case TTM_PROBE_BAND_EXPQ_FAR: r = band_expq_far(etab, x, kt); break;
+        case TTM_PROBE_BAND_LOG: r = band_log(x); break;
+        default: r = band_div(x, b[i]); break;
+    }
+    out[i] = r;
+}
+
+// ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
 static_assert(BAND_RT_KMAX == BAND_RING_KMAX, "k_band_inverse and the ring plan (ttm_band_image.h) cap a block at the same number of components");
@@ -2964,6 +2989,11 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
     auto kern = with_cls<3>(cls, [&](auto C) { return k_band_inverse<decltype(C)::value, 2, BAND_RT_KMAX>; });
     return launch(kern, cg.grid, b.lds, stream, "k_band_inverse", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, tab_x, T,
                   y_affine[0], y_affine[1], y_affine[2], tmin, tmax, bkt, nb, b.tab_slot, b.Bc, cg.rows, b.w0, b.W);
+}
+
+int math_probe(int which, const double* a, const double* b, int64_t n, double* out, void* stream, const char** kernel_name) {
+    return launch(k_band_math_probe, (n + BAND_CT - 1) / BAND_CT, (size_t)BAND_ET_DOUBLES * 8, stream, "k_band_math_probe", kernel_name, which, a, b,
+                  n, out);
 }
 
 }  // namespace ttm_band

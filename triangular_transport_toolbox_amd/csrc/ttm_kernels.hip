@@ -28,6 +28,7 @@
 
 #include "ttm_eval.h"
 #include "ttm_dev.h"
+#include "ttm_dense.h"
 #include "ttm_rng.h"
 #include "ttm_uform.h"
 #include "ttm_band.h"
@@ -1913,6 +1914,53 @@ __global__ __launch_bounds__(256) void k_basis(DevProg P, int k, int which, cons
         XSoA x{X, ldx, n};
         sample_basis(c, g, which, x, [&](int i, double v) { out[(int64_t)i * ldo + n] = v; });
     }
+}
+
+// ---------------------------------------------------------------------------
+// TEST HOOK (ttm_math_probe, include/ttm.h): the primitives of ttm_math.h / ttm_dense.h on arrays, one element per thread.
+// The erf table is staged by make_prog_lds (the loop of every kernel with special terms), the 2^(j/32) table of exp_q_tab
+// behind it by the same kind of loop; the series coefficients are the constant-memory arrays the primitives name
+// themselves.  The *_V2 ids: a thread takes the pair (2 t, 2 t + 1); the partner of the last element of an odd n is that
+// element again (loaded twice, stored once).  No map kernel calls this.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_math_probe(DevProg P, int which, const double* __restrict__ a, const double* __restrict__ b,
+                                                    int64_t n, double* __restrict__ out) {
+    double* slots;
+    CacheStore<double> cst;
+    const Prog g = make_prog_lds(P, cst, slots);
+    double* qtab = g_smem + TTM_ERF_TABLE_LEN;
+    for (int i = threadIdx.x; i < TTM_EXPQ_TABLE_LEN; i += blockDim.x) qtab[i] = g_expq_table[i];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (which == TTM_PROBE_FAST_EXP_V2 || which == TTM_PROBE_EXP_Q_FAST_V2) {
+        const int64_t i0 = 2 * i;
+        if (i0 >= n) return;
+        const int64_t i1 = i0 + 1 < n ? i0 + 1 : i0;
+        VecD<2> x;
+        x.v[0] = a[i0];
+        x.v[1] = a[i1];
+        const VecD<2> r = which == TTM_PROBE_FAST_EXP_V2 ? fast_exp(x) : exp_q_fast(x);
+        out[i0] = r.v[0];
+        if (i1 != i0) out[i1] = r.v[1];
+        return;
+    }
+    if (i >= n) return;
+    const double x = a[i];
+    double r, e, gs;
+    switch (which) {
+        case TTM_PROBE_FAST_EXP: r = fast_exp(x); break;
+        case TTM_PROBE_ERF_TAB: erf_gauss_tab<true>(g.erf_tab, x, e, gs); r = e; break;
+        case TTM_PROBE_GAUSS_TAB: erf_gauss_tab<true>(g.erf_tab, x, e, gs); r = gs; break;
+        case TTM_PROBE_FAST_LOG: r = fast_log(x); break;
+        case TTM_PROBE_FAST_RCP: r = fast_rcp(x); break;
+        case TTM_PROBE_FAST_DIV: r = fast_div(x, b[i]); break;
+        case TTM_PROBE_EXP_Q_TAB: r = exp_q_tab(qtab, x); break;
+        case TTM_PROBE_EXP_Q_FAST: r = exp_q_fast(x); break;
+        case TTM_PROBE_FAST_DIV1: r = fast_div1(x, b[i]); break;
+        case TTM_PROBE_APPROX_RCP: r = approx_rcp(x); break;
+        default: r = dense_exp_core(x); break;
+    }
+    out[i] = r;
 }
 
 // ---------------------------------------------------------------------------
@@ -4139,6 +4187,23 @@ int ttm_signal(double* flag, double value, void* stream) {
     if (!flag) return set_err(TTM_E_ARG, "ttm_signal: null flag%s");
     hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, (hipStream_t)stream, flag, value);
     return check_launch("k_signal");
+}
+
+int ttm_math_probe(int32_t which, const double* a, const double* b, int64_t n, double* out, void* stream) {
+    const bool band = which >= TTM_PROBE_BAND_EXPQ && which <= TTM_PROBE_BAND_DIV;
+    if (!band && (which < TTM_PROBE_FAST_EXP || which > TTM_PROBE_EXP_Q_FAST_V2)) return set_err(TTM_E_ARG, "ttm_math_probe: unknown primitive %s%lld", "", which);
+    const bool two = which == TTM_PROBE_FAST_DIV || which == TTM_PROBE_FAST_DIV1 || which == TTM_PROBE_BAND_DIV;
+    if (n < 0 || !a || !out || (two && !b)) return set_err(TTM_E_ARG, "ttm_math_probe: bad arguments%s");
+    if (n == 0) return TTM_OK;
+    if (band) {
+        const char* name = nullptr;
+        ttm_band::math_probe(which, a, b, n, out, stream, &name);
+        return check_launch(name);
+    }
+    DevProg P = {};                                  // (no program: make_prog_lds copies the fields, the probe reads the erf table only)
+    hipLaunchKernelGGL(k_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)(TTM_ERF_TABLE_LEN + TTM_EXPQ_TABLE_LEN) * 8,
+                       (hipStream_t)stream, P, (int)which, a, b, n, out);
+    return check_launch("k_math_probe");
 }
 
 }  // extern "C"

@@ -10,7 +10,10 @@
 //              coefficients give exp(-t^2) as the polynomial's derivative (11 more FMA, no exp call)
 //   fast_log : fdlibm-style log with a Newton reciprocal, ~35 instructions, <= 2 ulp
 //   fast_div : v_rcp_f64 + 2 Newton steps + residual correction (not IEEE-exact, <= 1 ulp)
-// Accuracy is tested against NumPy/SciPy in tests/test_math.py (host build of the same code).
+// Accuracy is tested against mpmath / NumPy twice: tests/test_math.py runs the HOST build of this header (where fast_rcp,
+// fast_div, fast_div1 and approx_rcp are plain IEEE divisions), tests/test_device_math.py the DEVICE build - the
+// v_rcp_f64 + Newton branches, the tables as the kernels stage them, the device lowering of rint / cvt / ldexp / frexp -
+// through the test hook ttm_math_probe (include/ttm.h), and the two builds against each other (<= 1 ulp).
 #pragma once
 
 #include <math.h>
