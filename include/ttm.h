@@ -530,7 +530,15 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
  *   iteration count over the processed samples (atomic max).
  * cap (nullable, int32, length k1-k0): when given, every sample stops after cap[k-k0] midpoint
  *   iterations - used to replay global sample 0 under the reference's `np.sum(indices) > 0`
- *   loop guard (TM:3952).                                                                          */
+ *   loop guard (TM:3952).
+ * Banded separable maps with push records take the same search in push form under the size gate of
+ * the table inverse when no cap is given (k_band_bisect / k_band_few_bisect, csrc/ttm_band.hip: the
+ * monotone part is the component's resident spline; option band_bisect = 0: the generic kernel).
+ * A call that starts on an odd row of 16-byte aligned matrices (Zsoa and Xsoa both 8 bytes past a
+ * 16-byte boundary, even leading dimensions with room for the pad row: what the host class passes
+ * to keep sample 0 out of iters) is split: its first row through the generic kernel, the rows behind
+ * it in push form, both into the same iters; nothing below Zsoa / Xsoa is read or written.  The
+ * size gate is held against the N of the call, not against the N - 1 rows behind the first.       */
 int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1,
                        const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
                        int32_t* iters, const int32_t* cap, void* stream);

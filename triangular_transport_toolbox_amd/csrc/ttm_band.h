@@ -48,6 +48,16 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
 int newton(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
            int32_t* iters, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name);
 
+// the reference's bisection (sample_bisect, csrc/ttm_eval.h: bracket +-2, window shifts, midpoints until |S - z| <= 1e-9 or 100
+// of them, the last midpoint returned; no cap - the capped replay of sample 0 stays with the generic kernel) in push form, planned
+// as newton().  iters: as ttm_inverse_bisect (midpoints).  1: declined
+int bisect(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
+           int32_t* iters, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name);
+
+// would bisect() take these arguments?  Its checks without a launch (the entry point asks before it splits a call)
+bool bisect_plans(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
+                  int32_t* iters, int cus, size_t lds_per_cu, int block);
+
 // forward map (+ log-determinant / sum of squares) and the table inverse of the image, in ONE launch, for maps of a few components
 // (k_band_few_roundtrip): Z (nullable) = S(X), Xr = S^-1(S(X)) - conditioning columns are read from X.  Without `force` only the
 // shapes the one launch is faster for (reach <= 2 columns, no density terms); 1: declined

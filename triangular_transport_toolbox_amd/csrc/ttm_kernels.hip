@@ -3280,6 +3280,12 @@ static bool band_newton_gate(const ttm_program* p, int k0, int k1, int64_t N) {
     return rt_shape_gate(p, k0, k1, N) && tuning().band_newton != 0 && ttm_band::usable(p, k0, k1);
 }
 
+// ... and does ttm_inverse_bisect take the reference's bisection in push form (k_band_bisect / k_band_few_bisect)?  The caller
+// checks that the call has no cap: the capped replay of sample 0 is the generic kernel's.
+static bool band_bisect_gate(const ttm_program* p, int k0, int k1, int64_t N) {
+    return rt_shape_gate(p, k0, k1, N) && tuning().band_bisect != 0 && ttm_band::usable(p, k0, k1);
+}
+
 int64_t ttm_fold_size(const ttm_program* p) {
     if (!p || !p->h_fold_off) return -1;
     return fold_base_size(p) + (p->u_enabled ? p->u_size : 0);
@@ -3793,6 +3799,31 @@ int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* f
             return check_launch(name);
     }
     auto kern = p->monotonicity == TTM_MONO_SEPARABLE ? k_inverse_bisect<TTM_MONO_SEPARABLE, false> : k_inverse_bisect<TTM_MONO_INTEGRATED, false>;
+    // banded separable maps, every row to convergence (no cap): the same search in push form (csrc/ttm_band.hip); a declined
+    // call runs the generic kernel
+    if (!cap && band_bisect_gate(p, k0, k1, N)) {
+        const double* U = fold + fold_base_size(p);
+        const char* name = nullptr;
+        if (ttm_band::bisect(p, U, k0, k1, Zsoa, ldz, Xsoa, ldx, N, iters, band_cus(), device_info().lds_per_cu, tuning().rt_block, stream, &name) == 0)
+            return check_launch(name);
+        // A call that starts on an odd row of 16-byte aligned matrices (the host class passes row 1 on: sample 0 must not count
+        // into iters): the first row through the generic kernel, the rows behind it - aligned - in push form, both into the
+        // same iters (the gate above is held against the rows of the call, not against the rows left).  Nothing is read or
+        // written below Zsoa / Xsoa; the pad row of an odd tail is row N of the columns, inside their leading dimensions.  Any
+        // other misalignment stays with the generic kernel.
+        const int64_t need = 1 + ((N & ~(int64_t)1));          // (1 + the rows behind the first rounded up to even)
+        if (N >= 2 && (uintptr_t)Zsoa % 16 == 8 && (uintptr_t)Xsoa % 16 == 8 && ldz % 2 == 0 && ldx % 2 == 0 && ldz >= need && ldx >= need &&
+            ttm_band::bisect_plans(p, U, k0, k1, Zsoa + 1, ldz, Xsoa + 1, ldx, N - 1, iters, band_cus(), device_info().lds_per_cu, tuning().rt_block)) {
+            hipLaunchKernelGGL(kern, dim3(1), dim3(bd), lds_bytes(ns, bd, 0), (hipStream_t)stream, dev_prog(p), (int)k0, (int)k1, coef, fold, Zsoa,
+                               ldz, Xsoa, ldx, (int64_t)1, iters, (const int32_t*)nullptr);
+            rc = check_launch("k_inverse_bisect");
+            if (rc) return rc;
+            if (ttm_band::bisect(p, U, k0, k1, Zsoa + 1, ldz, Xsoa + 1, ldx, N - 1, iters, band_cus(), device_info().lds_per_cu, tuning().rt_block,
+                                 stream, &name) == 0)
+                return check_launch(name);
+            // (a launch error: reported by the launch below)
+        }
+    }
     hipLaunchKernelGGL(kern, dim3(grid_for(N, bd)), dim3(bd), lds_bytes(ns, bd, 0), (hipStream_t)stream, dev_prog(p), (int)k0, (int)k1,
                        coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, cap);
     return check_launch("k_inverse_bisect");

@@ -26,6 +26,7 @@
     X(band_cus, -1)      /* > 0: the band kernels plan their row chunks for this many CUs (tests: several tiles per chunk) */ \
     X(band_ring, -1)     /* 0: banded table inverse through k_band_inverse (tables assembled per block) although images are at hand */ \
     X(band_newton, -1)   /* 0: Newton root search of banded maps through the generic k_inverse_newton instead of the push-form kernels */ \
+    X(band_bisect, -1)   /* 0: bisection of banded maps (no cap) through the generic k_inverse_bisect instead of the push-form kernels */ \
     X(int_dense, -1)     /* 0: integrated maps with dense B sets through the generic kernels instead of csrc/ttm_int.hip */ \
     X(int_xprog, -1)     /* 0: integrated components without their X programs (csrc/ttm_xprog.h: forward map, objective / gradient sums); \
                             2: the root searches through them as well (measured: the weights are 1 % of a bisection - no gain, 5 % slower at C2a) */ \
