@@ -20,10 +20,12 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
+#include <utility>
 
 #include "ttm_band.h"
 #include "ttm_band_etab.h"
 #include "ttm_band_image.h"
+#include "ttm_band_policy.h"
 
 namespace ttm_band {
 
@@ -45,6 +47,8 @@ __host__ __device__ constexpr int rec_stride(int cls, int lag) { return (TTM_P_H
 #define BAND_CT 1024                                 /* threads per workgroup */
 #define BAND_NS 4                                    /* rows per thread: pairs (2t, 2t+1) of the two halves of a tile */
 #define BAND_PF 1                                    /* columns requested ahead of the one being evaluated */
+static_assert(BAND_POLICY_TILE_ROWS == BAND_NS * BAND_CT && BAND_POLICY_HALF_ROWS == 2 * BAND_CT && BAND_NS == 4,
+              "ttm_band_policy.h counts the rows of pair slot 0 of these tiles");
 
 // One LDS-DMA instruction (16 bytes per lane: the wave's 1 KB lands at lds_wave_base, an LDS byte address, lane after lane),
 // written in assembly so that the COMPILER DOES NOT KNOW IT: with a global_load_lds it knows to be in flight hipcc waits for
@@ -138,8 +142,11 @@ __global__ __launch_bounds__(64) void k_band_records(const int* __restrict__ uco
     }
 }
 
-// column stream accesses: 16 bytes per lane.  The forward map and the inverse load and store plainly: what one launch leaves
-// in the Infinity Cache is what the next one reads.  The few-component kernels' column stores are non-temporal.
+// column stream accesses: 16 bytes per lane, plain or non-temporal (NT: `nt` on the instruction - the line does not allocate
+// in the Infinity Cache).  Which of them a long kernel's streams take is its policy POL (k_band_forward, k_band_inverse_ring;
+// ttm_band_policy.h): POL = 0 loads and stores plainly - what one launch leaves in the Infinity Cache is what the next one
+// reads, as long as the pair's buffers fit it; POL = 1 lets only pair slot 0 of every tile allocate (band_z_nt) and
+// streams everything else past it.  The few-component kernels' column stores are non-temporal; every other kernel is plain.
 template <bool NT>
 __device__ __forceinline__ void band_store2(char* p, double a, double b) {
     typedef double v2 __attribute__((ext_vector_type(2)));
@@ -147,12 +154,25 @@ __device__ __forceinline__ void band_store2(char* p, double a, double b) {
     if (NT) __builtin_nontemporal_store(v, (v2*)p);
     else *(v2*)p = v;
 }
+template <bool NT = false>
 __device__ __forceinline__ D2 band_load2(const char* p) {
     typedef double v2 __attribute__((ext_vector_type(2)));
-    const v2 v = *(const v2*)p;
+    v2 v;
+    if (NT) v = __builtin_nontemporal_load((const v2*)p);
+    else v = *(const v2*)p;
     const D2 r = {v.x, v.y};
     return r;
 }
+// POL = 1: the rows of pair slot q = 0 - the first half of every tile - are the part of Z that stays in the Infinity Cache from
+// the forward map to the inverse; is the access of Z in slot Q non-temporal?
+template <int POL, int Q> constexpr bool band_z_nt = POL != 0 && Q != 0;
+// f(std::integral_constant<int, q>) for q = 0 .. N - 1: the loop over a thread's pair slots where the slot has to be a CONSTANT OF
+// THE TYPE SYSTEM.  The policy of an access is part of the instruction; chosen by `if (q ...)` on the counter of an unrolled loop, the
+// two accesses of one address are merged into one plain access before the loop is unrolled (seen in the assembly: no `nt` left).
+template <class F, int... Q>
+__device__ __forceinline__ void band_slots_seq(F& f, std::integer_sequence<int, Q...>) { (f(std::integral_constant<int, Q>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void band_slots(F&& f) { band_slots_seq(f, std::make_integer_sequence<int, N>{}); }
 
 // ---------------------------------------------------------------------------
 // per-row pieces of a step
@@ -244,9 +264,35 @@ __device__ __forceinline__ double band_spline(const double* tab, int nI, double 
 // ---------------------------------------------------------------------------
 // forward map
 // ---------------------------------------------------------------------------
+// the two rows of pair slot q of a step: S, the pushes, the store (NT: non-temporal).  rec: the step's record; xc: its column.
+// What band_forward_tile's POL = 1 steps call; its POL = 0 steps have the same statements written out (see there)
+template <int CLS, int LAG, bool FULL, bool OWN, bool NT>
+__device__ __forceinline__ void band_forward_rows(int q, const D2 (&xc)[BAND_NS / 2], double (&pend)[BAND_NS][LAG], cdbl_p rec, double start, double sp_a,
+                                                  double sp_b, double sp_ds, double own1, int nI, const double* tab, const double* etab, cdbl_p kt,
+                                                  unsigned int tbase, char* zcol, unsigned int c1_32) {
+    constexpr int DB = cls_db(CLS), DA = cls_da(CLS), HALF = 2 * BAND_CT;
+    double zv[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int e = 2 * q + h;
+        const double x = h ? xc[q].y : xc[q].x;
+        const double m = (!OWN || nI > 0) ? band_spline(tab, nI, sp_a, sp_b, sp_ds, x) : 0.0;
+        const double E = band_expq(etab, x, kt);
+        zv[h] = OWN ? fma(own1, x, pend[e][0] + m) : pend[e][0] + m;     // (x 0 too: a NaN / infinite sample stays NaN)
+        band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, x, E, pend[e]);
+    }
+    const unsigned int n = tbase + (unsigned int)(q * HALF);
+    const D2 o = {zv[0], zv[1]};
+    char* zp = zcol + (size_t)(n * 8u);
+    if (FULL || n + 1 < c1_32) band_store2<NT>(zp, o.x, o.y);
+    else if (n < c1_32) *(double*)zp = o.x;
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // the columns [kb, ke) of one tile; FULL: every row of the tile exists (unmasked stores); OWN: some component of the map has
-// a linear term of its own variable next to its spline or instead of it (slot [7] of the record; NI = 0: no spline)
-template <int CLS, int LAG, bool FULL, bool OWN>
+// a linear term of its own variable next to its spline or instead of it (slot [7] of the record; NI = 0: no spline);
+// POL = 1: X is loaded non-temporally, Z stored plainly in pair slot 0 and non-temporally in slot 1 (band_z_nt)
+template <int CLS, int LAG, bool FULL, bool OWN, int POL = 0>
 __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const double* etab, const double* tabs, int tab0, int kb, int ke,
                                                   const char* xcol, int64_t ldxb, char* zcol, int64_t ldzb, unsigned int tbase,
                                                   const unsigned int (&roff)[BAND_NS / 2], unsigned int c1_32,
@@ -262,14 +308,14 @@ __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const dou
     for (int i = 0; i < PF; ++i) {
         const char* xc0 = xcol + (int64_t)(kb + i < ke ? i : 0) * ldxb;
 #pragma unroll
-        for (int q = 0; q < NP; ++q) xr[i][q] = band_load2(xc0 + roff[q]);
+        for (int q = 0; q < NP; ++q) xr[i][q] = band_load2<POL != 0>(xc0 + roff[q]);
     }
     cdbl_p rec = P + (int64_t)(kb + LAG) * PS;
     auto step = [&](int j, const D2 (&xc)[NP], D2 (&xn)[NP]) {
         {
             const char* xnext = j + PF < ke ? xcol + PF * ldxb : xcol;        // (past the block: a harmless re-read)
 #pragma unroll
-            for (int q = 0; q < NP; ++q) xn[q] = band_load2(xnext + roff[q]);
+            for (int q = 0; q < NP; ++q) xn[q] = band_load2<POL != 0>(xnext + roff[q]);
         }
         __builtin_amdgcn_sched_barrier(0);                    // (the scheduler would sink the loads to the end of the step)
         // ---- uniform data of the step ------------------------------------------------------------------------
@@ -280,24 +326,35 @@ __device__ __forceinline__ void band_forward_tile(cdbl_p P, cdbl_p kt, const dou
         const double* tab = tabs + (ri[11] - tab0);
         // ---- row by row (two of them scheduled together: each needs 24 registers for its coefficients; the waves of the
         // SIMD, not the rows of a thread, fill each other's latencies) -------------------------------------------------
+        if constexpr (POL == 0) {
+            // (band_forward_rows<..., false>, written out: called as a function - or a lambda - in this loop, the same statements
+            // moved the spills of k_band_forward<2, 2, true> and <3, 2, true>, 29 -> 33 and 28 -> 29 VGPRs, scratch 116 -> 180 bytes:
+            // OPTLOG round 12 item 3.  The plain policy keeps the code it was measured with; a change to a row goes into both)
 #pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            double zv[2];
+            for (int q = 0; q < NP; ++q) {
+                double zv[2];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int e = 2 * q + h;
-                const double x = h ? xc[q].y : xc[q].x;
-                const double m = (!OWN || nI > 0) ? band_spline(tab, nI, sp_a, sp_b, sp_ds, x) : 0.0;
-                const double E = band_expq(etab, x, kt);
-                zv[h] = OWN ? fma(own1, x, pend[e][0] + m) : pend[e][0] + m;     // (x 0 too: a NaN / infinite sample stays NaN)
-                band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, x, E, pend[e]);
+                for (int h = 0; h < 2; ++h) {
+                    const int e = 2 * q + h;
+                    const double x = h ? xc[q].y : xc[q].x;
+                    const double m = (!OWN || nI > 0) ? band_spline(tab, nI, sp_a, sp_b, sp_ds, x) : 0.0;
+                    const double E = band_expq(etab, x, kt);
+                    zv[h] = OWN ? fma(own1, x, pend[e][0] + m) : pend[e][0] + m;     // (x 0 too: a NaN / infinite sample stays NaN)
+                    band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, x, E, pend[e]);
+                }
+                const unsigned int n = tbase + (unsigned int)(q * HALF);
+                const D2 o = {zv[0], zv[1]};
+                char* zp = zcol + (size_t)(n * 8u);
+                if (FULL || n + 1 < c1_32) band_store2<false>(zp, o.x, o.y);
+                else if (n < c1_32) *(double*)zp = o.x;
+                __builtin_amdgcn_sched_barrier(0);
             }
-            const unsigned int n = tbase + (unsigned int)(q * HALF);
-            const D2 o = {zv[0], zv[1]};
-            char* zp = zcol + (size_t)(n * 8u);
-            if (FULL || n + 1 < c1_32) band_store2<false>(zp, o.x, o.y);
-            else if (n < c1_32) *(double*)zp = o.x;
-            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            // (the slot as a constant of the type system: the policy of the store depends on it)
+            band_slots<NP>([&](auto Q) {
+                constexpr int q = decltype(Q)::value;
+                band_forward_rows<CLS, LAG, FULL, OWN, band_z_nt<POL, q>>(q, xc, pend, rec, start, sp_a, sp_b, sp_ds, own1, nI, tab, etab, kt, tbase, zcol, c1_32);
+            });
         }
         rec += PS; xcol += ldxb; zcol += ldzb;
     };
@@ -775,7 +832,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_logdet(const double* __restric
 }
 
 // LDS: [E table: 2 x 801 | splines of the block's components, as they stand in the U section]
-template <int CLS, int LAG, bool OWN>
+// POL: the cache policy of the column streams (band_store2 ff.; the host's choice: ttm_band_policy.h)
+template <int CLS, int LAG, bool OWN, int POL = 0>
 __global__ __launch_bounds__(BAND_CT) void k_band_forward(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                           const double* __restrict__ X, int64_t ldx, int64_t N,
                                                           double* __restrict__ Z, int64_t ldz, int64_t rows_per_wg, int Bc) {
@@ -844,8 +902,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_forward(const double* __restri
             }
             const char* xcol = (const char*)X + (int64_t)colb * ldxb;
             char* zcol = (char*)Z + (int64_t)(kb - k0) * ldzb;
-            if (full) band_forward_tile<CLS, LAG, true, OWN>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
-            else band_forward_tile<CLS, LAG, false, OWN>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
+            if (full) band_forward_tile<CLS, LAG, true, OWN, POL>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
+            else band_forward_tile<CLS, LAG, false, OWN, POL>(P, kt, etab, tabs, tab0, kb, ke, xcol, ldxb, zcol, ldzb, tbase, roff, c1_32, pend);
         }
     }
 }
@@ -1144,7 +1202,9 @@ __device__ __forceinline__ void band_ring_fill(const double* img, int ncomp, dou
     }
 }
 
-template <int CLS, int LAG, bool RING = false, int G = 0>
+// POL = 1 (the ring kernel only): Z is loaded plainly in pair slot 0 and non-temporally in slot 1 (band_z_nt), X stored
+// non-temporally; a partial tile's single rows, the DMA pieces and the outlier path's table reads stay plain
+template <int CLS, int LAG, bool RING = false, int G = 0, int POL = 0>
 __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool full, int kb, int ke, const char* zcol, char* xcol, unsigned int tbase,
                                                   const unsigned int (&roff)[BAND_NS / 2], double (&pend)[BAND_NS][LAG],
                                                   const D2 (&zfirst)[BAND_NS / 2], bool have_first, BandRing* rg = nullptr) {
@@ -1160,8 +1220,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
 #pragma unroll
         for (int q = 0; q < NP; ++q) za[q] = zfirst[q];
     } else {
-#pragma unroll
-        for (int q = 0; q < NP; ++q) za[q] = band_load2(zcol + roff[q]);
+        band_slots<NP>([&](auto Q) { constexpr int q = decltype(Q)::value; za[q] = band_load2<band_z_nt<POL, q>>(zcol + roff[q]); });
     }
     // interp1d slope form (TM:4062-4065) in the located interval and exp(-x^2/4) = E[i-1] exp(w), w = -delta (y_lo + x) / 4
     auto interp = [&](double y_lo, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
@@ -1183,8 +1242,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
     auto step = [&](int j, const D2 (&zc)[NP], D2 (&zn)[NP]) {
         {
             const char* znext = j + 1 < ke ? zcol + cx.ldzb : zcol;           // (past the block: a harmless re-read)
-#pragma unroll
-            for (int q = 0; q < NP; ++q) zn[q] = band_load2(znext + roff[q]);
+            band_slots<NP>([&](auto Q) { constexpr int q = decltype(Q)::value; zn[q] = band_load2<band_z_nt<POL, q>>(znext + roff[q]); });
         }
         // the record of the step, requested NOW (left to itself the compiler loads the group coefficients where the pushes
         // use them - at the end of the step's dependent chain, a scalar-cache round trip on the critical path)
@@ -1281,7 +1339,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
         if (full) {
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
-                band_store2<false>(xcol + (size_t)((tbase + (unsigned int)(q * HALF)) * 8u), r[2 * q], r[2 * q + 1]);
+                band_store2<POL != 0>(xcol + (size_t)((tbase + (unsigned int)(q * HALF)) * 8u), r[2 * q], r[2 * q + 1]);
             }
         } else {
 #pragma unroll
@@ -1289,7 +1347,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
                 const unsigned int n = tbase + (unsigned int)(q * HALF);
                 const D2 o = {r[2 * q], r[2 * q + 1]};
                 char* xp = xcol + (size_t)(n * 8u);
-                if (n + 1 < cx.c1_32) *(D2*)xp = o;
+                if (n + 1 < cx.c1_32) { if (POL != 0) band_store2<true>(xp, o.x, o.y); else *(D2*)xp = o; }
                 else if (n < cx.c1_32) *(double*)xp = o.x;
             }
         }
@@ -1492,7 +1550,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse(const double* __restri
 // ahead of their use.  A tile walks ALL its columns in one go: the running sums never leave the registers, so the result of a
 // row does not depend on the chunking (k_band_inverse re-reads LAG columns at a block boundary when a chunk has several tiles
 // and takes their exp(-x^2/4) from the series there).  The step itself is band_inverse_tile, shared with k_band_inverse.
-template <int CLS, int LAG, int G>
+// POL: the cache policy of the column streams (band_inverse_tile; the host's choice: ttm_band_policy.h)
+template <int CLS, int LAG, int G, int POL = 0>
 __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                                const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
                                                                const double* __restrict__ tab_x, int T, double y0, double ystep, double ylast,
@@ -1536,12 +1595,12 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
     }
     // the first column of z of the first tile, then the images of the first R steps: one memory round trip
     D2 zfirst[NP];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
+    band_slots<NP>([&](auto Q) {
+        constexpr int q = decltype(Q)::value;
         unsigned int n = (unsigned int)c0 + 2u * (unsigned int)tid + (unsigned int)(q * HALF);
         n = n < last_pair ? n : last_pair;
-        zfirst[q] = band_load2((const char*)Z + (size_t)(n * 8u));
-    }
+        zfirst[q] = band_load2<band_z_nt<POL, q>>((const char*)Z + (size_t)(n * 8u));
+    });
     band_ring_fill(img, ncomp, tabs, tab_slot, R);
     for (int i = tid; i < W; i += CT) {
         etab[2 * i] = band_expq_series(w0 + i == T - 1 ? ylast : (double)(w0 + i) * ystep + y0);
@@ -1577,7 +1636,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
                 band_push<DB, DA, LAG>(rec + TTM_P_HDR, rec[1], xv.y, cc >= 0 ? band_expq_series(xv.y) : 1.0, pend[2 * q + 1]);
             }
         }
-        band_inverse_tile<CLS, LAG, true, G>(cx, full, k0, k1, (const char*)Z, (char*)X + (int64_t)kcol0 * ldxb, tbase, roff, pend, zfirst, tile == 0, &rg);
+        band_inverse_tile<CLS, LAG, true, G, POL>(cx, full, k0, k1, (const char*)Z, (char*)X + (int64_t)kcol0 * ldxb, tbase, roff, pend, zfirst, tile == 0, &rg);
     }
 }
 
@@ -3130,7 +3189,8 @@ static size_t block_lds_span(const ttm_program* p, int k0, int k1, int Bc, bool 
 }
 
 int forward(const ttm_program* p, const double* U, int k0, int k1, const double* Xsoa, int64_t ldx, int64_t N, double* Zsoa, int64_t ldz,
-            double* logdet, const double* sigma, double* sumsq, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name) {
+            double* logdet, const double* sigma, double* sumsq, int cus, size_t lds_per_cu, int block, int resident, void* stream,
+            const char** kernel_name) {
     // (rows: 2^28 here, 2^29 at the gate in ttm_kernels.hip - both stand)
     if (!usable(p, k0, k1) || (!Zsoa && !logdet && !sumsq) || N >= ((int64_t)1 << 28)) return 1;
     // (need = 0 for Z: ldz is not held against N here, as it is in roundtrip() and newton())
@@ -3189,7 +3249,13 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
         return launch(dk, cg.grid, lds, stream, "k_band_density", kernel_name, U, p->u_p_off, k0, k1, kcol0, Xsoa, ldx, N, Zsoa, ldz, logdet, sigma,
                       sumsq, cg.rows, Bc);
     }
-    auto kern = with_bool(own, [&](auto OW) { return with_cls<3>(cls, [&](auto C) { return k_band_forward<decltype(C)::value, 2, decltype(OW)::value>; }); });
+    // the cache policy of the column streams (ttm_band_policy.h): a function of the sizes, or the option's
+    const bool pol = (band_resident_policy(N, cg.rows, k1 - k0, resident) & BAND_POLICY_FORWARD) != 0;
+    auto kern = with_bool(pol, [&](auto PO) {
+        return with_bool(own, [&](auto OW) {
+            return with_cls<3>(cls, [&](auto C) { return k_band_forward<decltype(C)::value, 2, decltype(OW)::value, decltype(PO)::value ? 1 : 0>; });
+        });
+    });
     return launch(kern, cg.grid, lds, stream, "k_band_forward", kernel_name, U, p->u_p_off, k0, k1, kcol0, Xsoa, ldx, N, Zsoa, ldz, cg.rows, Bc);
 }
 
@@ -3318,7 +3384,7 @@ static BlockPlan block_plan(int T, int W, int nb, int ncomp, size_t lds_per_cu, 
 // table inverse, in this order: the few-component kernel, the ring kernel (images at hand, laid out for this very plan), the block kernel
 int inverse(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
             const double* tab_x, int T, const double* y_affine, const double* tmin, const double* tmax, const int32_t* bkt, int nb, const double* img,
-            int img_doubles, int cus, size_t lds_per_cu, int window, int block, void* stream, const char** kernel_name) {
+            int img_doubles, int cus, size_t lds_per_cu, int window, int block, int resident, void* stream, const char** kernel_name) {
     if (!usable(p, k0, k1) || T < 64 || T > 4096 || nb + 1 != 1024 || N >= ((int64_t)1 << 28)) return 1;      // (bucket rows copied 16 bytes at a time, 256 units per row)
     if (!vec_ok(bkt) || !y_affine_ok(y_affine)) return 1;
     if (!col_ok(Zsoa, ldz, even_rows(N)) || !col_ok(Xsoa, ldx, even_rows(N))) return 1;
@@ -3346,8 +3412,13 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
     BandRingPlan pl;
     if (img && vec_ok(img) && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl) &&
         pl.tab_slot == img_doubles) {                         // (laid out for another plan - options changed in between: not this kernel)
-        auto rk = with_bool(pl.G == 4, [&](auto G4) {
-            return with_cls<3>(cls, [&](auto C) { return k_band_inverse_ring<decltype(C)::value, 2, decltype(G4)::value ? 4 : 0>; });
+        const bool pol = (band_resident_policy(N, cg.rows, ncomp, resident) & BAND_POLICY_INVERSE) != 0;      // (as forward())
+        auto rk = with_bool(pol, [&](auto PO) {
+            return with_bool(pl.G == 4, [&](auto G4) {
+                return with_cls<3>(cls, [&](auto C) {
+                    return k_band_inverse_ring<decltype(C)::value, 2, decltype(G4)::value ? 4 : 0, decltype(PO)::value ? 1 : 0>;
+                });
+            });
         });
         return launch(rk, cg.grid, pl.lds, stream, "k_band_inverse_ring", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, tab_x, T,
                       y_affine[0], y_affine[1], y_affine[2], tmin, tmax, img, nb, pl.tab_slot, pl.R, cg.rows, pl.w0, pl.W);
