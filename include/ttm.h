@@ -583,7 +583,11 @@ int ttm_objective_host(const ttm_program* p, int32_t k, const double* h_coef_k, 
  * ttm_basis(which = 2) (m rows of N doubles, row stride ldp) and every evaluation is one streaming launch:
  *   out[0] = sum_n log dS_n, out[1+i] = sum_n dPsi_{n,i}/dS_n, dS = dPsi.c + delta*rowsum(dPsi), m <= 16.
  * h_coef_mon: HOST vector of the m trial coefficients (kernel arguments).  work: >= ttm_reduce_work_size(1+m) doubles;
- * counter / out as ttm_objective_host.                                                                             */
+ * counter / out as ttm_objective_host.
+ * Range: a row whose dS is subnormal (0 < dS < 2^-1022: every dPsi_{n,i} that far down and no term that keeps dS up) has a
+ * reciprocal beyond the largest double - its log enters out[0] as it should, but out[1 + i] = +inf where the exact sums are
+ * finite.  A row with dS = 0 gives out[0] = -inf and NaN in out[1 + i], a NaN or infinite dPsi NaN everywhere, as NumPy
+ * does (tests/test_sep_objective.py).                                                                              */
 int ttm_objective_sep_cached(const double* dPsi, int64_t ldp, int64_t N, int32_t m, const double* h_coef_mon,
                              double delta, double* work, uint32_t* counter, double* out, void* stream);
 /* The two host-loop reductions with a completion mark: the finishing workgroup writes *flag = mark (flag: pinned host

@@ -336,23 +336,78 @@ def test_c_abi_reports_bad_arguments_instead_of_launching():
 @pytest.mark.parametrize('name', ['c5_sep', 'c3_sep', 'c2b_sep', 'c2a_int'])
 def test_gram_on_the_matrix_cores_equals_the_pairwise_kernel(name, ttm_opt):
     """G = Psi' Psi (TM:2966-2975) by v_mfma_f64_16x16x4f64 - one tile for up to 16 basis functions, three for up to 32 -
-    against the pairwise FMA kernel and against NumPy on the basis matrices: the same sums up to their order."""
+    against the pairwise FMA kernel and against NumPy on the basis matrices: the same sums up to their order.  The basis
+    matrices are what ttm_basis writes, [nonmon | mon], on the first N = 4099, 1, 3, 257 rows; Psi' Psi is formed in
+    np.longdouble and k_gram, k_gram_mfma and the batch kernel of ttm_gram_many are held to
+        |G_ij - ref_ij| <= (N + 8) u sum_n |Psi_ni Psi_nj|,  u = 2^-53:
+    N u covers any order of the sum, 8 u the kernels' own evaluation of the basis (2 ulp from ttm_basis per factor) and the
+    rounding of the product."""
+    from triangular_transport_toolbox_amd import _capi
     from triangular_transport_toolbox_amd.transport_map import transport_map
     npz, desc = load_case(name)
     X = case_X(name, npz)
     X = np.concatenate([X + 0.01 * i for i in range(5)])[:4099]          # several tiles and a ragged last one
     tm = transport_map(X=X, monotone=desc['monotone'], nonmonotone=desc['nonmonotone'], verbose=False, **ctor_kwargs(desc))
-    seen = set()
-    for k in range(tm.D):
-        ttm_opt('gram_mfma', 0)
-        G0 = tm._gram(k)
-        assert tm._lib.ttm_last_kernel().decode() == 'k_gram'
-        ttm_opt('gram_mfma', 1)
-        G1 = tm._gram(k)
-        m = G0.shape[0]
-        if m <= 32:
-            assert tm._lib.ttm_last_kernel().decode() == 'k_gram_mfma'
-            seen.add(m > 16)
-        assert np.array_equal(G1, G1.T)
-        assert np.max(np.abs(G1 - G0)) <= 1e-14 * np.max(np.abs(G0))             # (entries that cancel to ~0 differ by rounding only)
+    lib, Xs, ld, st = tm._lib, tm._ptr(tm._Xs), tm._Xs.shape[1], tm._stream()
+    sizes = [int(tm._cm.n_nm[k] + tm._cm.n_mon[k]) for k in range(tm.D)]
+    work = tm._empty(int(lib.ttm_reduce_work_size(max(sizes) ** 2)))
+
+    def gram(k, N):
+        out = tm._empty(sizes[k] ** 2)
+        _capi.check(lib.ttm_gram(tm._pp, int(k), Xs, ld, N, tm._ptr(work), tm._ptr(out), st))
+        return out.cpu().numpy().reshape(sizes[k], sizes[k])
+
+    def reference(k, N):
+        """(Psi' Psi, bound) from the columns ttm_basis writes, in np.longdouble"""
+        assert np.finfo(np.longdouble).nmant >= 63
+        cols = []
+        for which, n in ((0, int(tm._cm.n_nm[k])), (1, int(tm._cm.n_mon[k]))):
+            if n:
+                out = tm._empty(n, N)
+                _capi.check(lib.ttm_basis(tm._pp, int(k), which, Xs, ld, N, tm._ptr(out), N, st))
+                cols.append(out.cpu().numpy())
+        P = np.concatenate(cols).astype(np.longdouble)
+        return P @ P.T, (N + 8) * 2.0 ** -53 * (np.abs(P) @ np.abs(P).T)
+
+    seen, seen_many, worst = set(), False, 0.0
+    for N in (tm._N, 1, 3, 257):
+        refs = {}
+        for k in range(tm.D):
+            ttm_opt('gram_mfma', 0)
+            G0 = tm._gram(k) if N == tm._N else gram(k, N)
+            assert tm._lib.ttm_last_kernel().decode() == 'k_gram'
+            ttm_opt('gram_mfma', 1)
+            G1 = tm._gram(k) if N == tm._N else gram(k, N)
+            m = G0.shape[0]
+            if m <= 32:
+                assert tm._lib.ttm_last_kernel().decode() == 'k_gram_mfma'
+                seen.add(m > 16)
+            assert np.array_equal(G1, G1.T)
+            assert np.max(np.abs(G1 - G0)) <= 1e-14 * np.max(np.abs(G0))             # (entries that cancel to ~0 differ by rounding only)
+            ref, bound = refs[k] = reference(k, N)
+            for kern, G in (('k_gram', G0), ('k_gram_mfma', G1)):
+                err = np.abs(G.astype(np.longdouble) - ref)
+                worst = max(worst, float(np.max(err[bound > 0] / bound[bound > 0])))
+                assert np.all(err <= bound), (kern, k, N, float(np.max(err / np.where(bound > 0, bound, 1))))
+        # the batch kernel: up to eight components per launch, the blocks one behind the other
+        for k0 in range(0, tm.D, 8):
+            ks = np.arange(k0, min(k0 + 8, tm.D), dtype=np.int32)
+            out = tm._empty(sum(sizes[k] ** 2 for k in ks))
+            rc = lib.ttm_gram_many(tm._pp, ctypes.c_void_p(ks.ctypes.data), len(ks), Xs, ld, N, tm._ptr(work), tm._ptr(out), st)
+            if rc == _capi.TTM_E_UNSUPPORTED:               # (more than 16 basis functions, block sizes that differ: ttm_gram per component)
+                continue
+            _capi.check(rc)
+            assert tm._lib.ttm_last_kernel().decode() == 'k_gram_mfma_many'
+            seen_many = True
+            flat, o = out.cpu().numpy(), 0
+            for k in ks:
+                G = flat[o:o + sizes[k] ** 2].reshape(sizes[k], sizes[k])
+                o += sizes[k] ** 2
+                ref, bound = refs[int(k)]
+                err = np.abs(G.astype(np.longdouble) - ref)
+                worst = max(worst, float(np.max(err[bound > 0] / bound[bound > 0])))
+                assert np.all(err <= bound), ('k_gram_mfma_many', int(k), N, float(np.max(err / np.where(bound > 0, bound, 1))))
+    from tests.util import record_parity
+    record_parity('gram/%s/error_over_bound' % name, worst, 1.0)
     assert seen                                                          # (the matrix-core kernel ran)
+    assert seen_many or name != 'c5_sep'                                 # (... and the batch kernel, on the map it was written for)

@@ -2452,6 +2452,14 @@ __global__ __launch_bounds__(256) void k_fill_bits(unsigned long long* __restric
 #define TTM_SEPC_MAXM 16
 struct SepCoef { double c[TTM_SEPC_MAXM]; };
 
+// 1 / dS of a row.  A SUBNORMAL dS (every dPsi of the row below ~1e-300 and no term that keeps dS up) has a reciprocal beyond the
+// largest double: v_rcp_f64 returns +inf, of which the Newton steps of fast_rcp make inf - inf = NaN.  The reciprocal stays +inf, as
+// the division of the host build gives it: gradient sums of +inf there, never NaN (include/ttm.h states the limit).
+__device__ __forceinline__ double sep_rcp(double dS) {
+    const double r = fast_rcp(dS);
+    return dS > 0.0 && dS < 2.2250738585072014e-308 ? __builtin_huge_val() : r;
+}
+
 template <int M>
 __global__ __launch_bounds__(256) void k_objective_sep_cached(const double* __restrict__ dPsi, int64_t ldp, int64_t N,
                                                               SepCoef hc, double delta, double* __restrict__ partial,
@@ -2475,7 +2483,7 @@ __global__ __launch_bounds__(256) void k_objective_sep_cached(const double* __re
         }
         dS += rowsum * delta;
         acc[0] += fast_log(dS);
-        const double inv = fast_rcp(dS);
+        const double inv = sep_rcp(dS);
 #pragma unroll
         for (int i = 0; i < M; ++i) acc[1 + i] += d[i] * inv;
     };
@@ -2577,7 +2585,7 @@ __global__ __launch_bounds__(256) void k_objective_sep_server(const double* __re
             }
             dS += rowsum * delta;
             acc[0] += fast_log(dS);
-            const double inv = fast_rcp(dS);
+            const double inv = sep_rcp(dS);
 #pragma unroll
             for (int i = 0; i < M; ++i) acc[1 + i] += d[i] * inv;
         };
@@ -2650,7 +2658,7 @@ __global__ __launch_bounds__(256) void k_objective_sep_direct(const double* __re
         }
         dS += rowsum * delta;
         acc[0] += fast_log(dS);
-        const double inv = fast_rcp(dS);
+        const double inv = sep_rcp(dS);
 #pragma unroll
         for (int i = 0; i < M; ++i) acc[1 + i] += d[i] * inv;
     };
