@@ -534,6 +534,8 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
  * Banded separable maps with push records take the same search in push form under the size gate of
  * the table inverse when no cap is given (k_band_bisect / k_band_few_bisect, csrc/ttm_band.hip: the
  * monotone part is the component's resident spline; option band_bisect = 0: the generic kernel).
+ * Both names, like k_band_newton / k_band_few_newton below, are instantiations of one template per
+ * shape (k_band_search / k_band_few_search); ttm_last_kernel reports the names given here.
  * A call that starts on an odd row of 16-byte aligned matrices (Zsoa and Xsoa both 8 bytes past a
  * 16-byte boundary, even leading dimensions with room for the pad row: what the host class passes
  * to keep sample 0 out of iters) is split: its first row through the generic kernel, the rows behind
@@ -552,7 +554,8 @@ int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* f
  * ttm_inverse_bisect.  iters: as above (maximum number of Newton / midpoint trial points).
  * Banded separable maps with push records take the same search in push form under the size gate of
  * the table inverse (k_band_newton / k_band_few_newton, csrc/ttm_band.hip: the monotone part is the
- * component's resident spline; option band_newton = 0: the generic kernel).                       */
+ * component's resident spline; option band_newton = 0: the generic kernel; the names are those
+ * reported for the Newton instantiations of k_band_search / k_band_few_search).                   */
 int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1,
                        const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
                        int32_t* iters, void* stream);

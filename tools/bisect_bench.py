@@ -5,7 +5,8 @@ alternate_root_finding=False: the launch on rows 1.., then the replay of sample 
 
 Workloads: C5 N = 1e6, C2b N = 1e6, C3 N = 5e5 (bench.py's maps and coefficient fixtures).  Versions, alternated round by
 round within the one process after a warm-up of every shape (the chip holds its clock only while it is kept busy: bench.py):
-  bisect   as the library plans it (k_band_bisect / k_band_few_bisect where the build has them, else k_inverse_bisect)
+  bisect   as the library plans it (k_band_bisect / k_band_few_bisect where the build has them, else k_inverse_bisect; with the Newton
+           kernels instantiations of one template per shape, k_band_search / k_band_few_search)
   generic  the same call with option band_bisect = 0 (k_inverse_bisect) - left out where the library does not know the option
   newton   ttm_inverse_newton of the same build (k_band_newton / k_band_few_newton)
   table    the table inverse of the same build (k_band_inverse_ring / k_band_few_inverse), tables built beforehand

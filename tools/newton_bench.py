@@ -4,7 +4,8 @@
 
 Workloads: C5 N = 1e6, C2b N = 1e6, C3 N = 5e5 (bench.py's maps and coefficient fixtures).  Versions, alternated round by
 round within the one process after a warm-up of every shape (the chip holds its clock only while it is kept busy: bench.py):
-  newton   root_finder='newton' as the library plans it (k_band_newton / k_band_few_newton)
+  newton   root_finder='newton' as the library plans it (k_band_newton / k_band_few_newton: with the bisection kernels
+           instantiations of one template per shape, k_band_search / k_band_few_search)
   generic  the same call with option band_newton = 0 (k_inverse_newton) - left out where the library does not know the option
   table    the table inverse of the same build (k_band_inverse_ring / k_band_few_inverse), tables built beforehand
 HIP events around every batch of launches; per version the median over the rounds of the mean launch time and the spread

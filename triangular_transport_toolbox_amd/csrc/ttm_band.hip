@@ -2252,15 +2252,22 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
 }
 
 // ---------------------------------------------------------------------------
-// safeguarded Newton root search in push form (root_finder = 'newton', ttm_inverse_newton): S_c(x) = z_c with
-// S_c(x) = pend[0] + own1 x + G_c(x), G_c the component's resident spline - no inverse tables, no images.  The iteration is
-// sample_newton's (csrc/ttm_eval.h), statement for statement, on the rows of a thread at once: bracket [-2, 2], window
-// doubling (at most 2000 shifts), secant start, Newton step with dS/dx, midpoint whenever the step leaves the bracket (a zero
-// derivative sends it to infinity: midpoint), stop at |S - z| <= 1e-9 or 100 trial points; a row without a sign change (NaN
-// target, a component that is not monotone) ends at the last bracket point tried.  A finished row keeps its result and
-// rides along (selects, no branches), so the dependent chains of the rows overlap; the loops end when every lane is done.
-// The residual is taken against t = z - pend[0], the target of the monotone part (what band_inverse_tile looks up): one
-// running value per row instead of two through the loops.
+// root searches in push form: S_c(x) = z_c with S_c(x) = pend[0] + own1 x + G_c(x), G_c the component's resident spline - no
+// inverse tables, no images.  One routine, band_search_rows, on the rows of a thread at once.  Both methods open alike:
+// bracket [-2, 2], its ends swapped where flo > fhi, shifted by twice its width while both values lie on one side of zero (at
+// most 2000 shifts; flo = 0 or a NaN ends them).  BIS then selects the tail:
+//  - safeguarded Newton (root_finder = 'newton', ttm_inverse_newton): the iteration is sample_newton's (csrc/ttm_eval.h),
+//    statement for statement: secant start, Newton step with dS/dx, midpoint whenever the step leaves the bracket (a zero
+//    derivative sends it to infinity: midpoint), stop at |S - z| <= 1e-9 or 100 trial points; a row without a sign change (NaN
+//    target, a component that is not monotone) ends at the last bracket point tried.
+//  - the reference's bisection (root_finder = 'reference', ttm_inverse_bisect without a cap): sample_bisect (csrc/ttm_eval.h)
+//    statement for statement: midpoints only - lo = mid where fm < 0, hi = mid where fm > 0, stop at !(|fm| > 1e-9) or after
+//    100 midpoints.  There is no exit for a bracket without a sign change (sample_newton has one): whatever bracket the shifts
+//    end with is bisected, and a NaN target stops at the first midpoint, 0.  No derivative, no division: the loop's state is
+//    lo, hi, t and r per row.
+// A finished row keeps its result and rides along (selects, no branches), so the dependent chains of the rows overlap; the
+// loops end when every lane is done.  The residual is taken against t = z - pend[0], the target of the monotone part (what
+// band_inverse_tile looks up): one running value per row instead of two through the loops.
 // ---------------------------------------------------------------------------
 // a / b: reciprocal + two Newton steps + one correction of the quotient (b = 0, infinite or NaN: not a finite quotient)
 __device__ __forceinline__ double band_div(double a, double b) {
@@ -2279,12 +2286,14 @@ __device__ __forceinline__ double band_expq_far(const double* etab, double x, cd
     return fabs(x) > 60.0 ? 0.0 : E;
 }
 
-// sp(der, x, g, dg): the spline and (der) its derivative with respect to the local coordinate; sp_ds: d local / dx.
-// t: the rows' targets of the monotone part, r: the last trial points; live: the row is one of the caller's own (a row that
-// is not searches nothing and counts nothing: r = +2).  Returns the most trial points a live row needed.
-// (TWIN: band_bisect_rows below carries a copy of the bracket and window-shift half of this routine)
-template <int NS, bool OWN, class SP>
-__device__ __forceinline__ int band_newton_rows(const SP& sp, double own1, double sp_ds, const double (&t)[NS], const bool (&live)[NS],
+// sp(der, x, g, dg): the spline and (der) its derivative with respect to the local coordinate; sp_ds: d local / dx (the
+// bisection ignores it).  t: the rows' targets of the monotone part, r: the last trial points (BIS: the last midpoints); live:
+// the row is one of the caller's own (a row that is not searches nothing and counts nothing: r = +2).  Returns the most trial
+// points (BIS: midpoints) a live row needed.
+// (The bracket stays in this function: as a routine of its own, its four arrays by reference, it changes the register
+// allocation of the Newton kernels - OPTLOG rounds 11 and 13.)
+template <int NS, bool OWN, bool BIS, class SP>
+__device__ __forceinline__ int band_search_rows(const SP& sp, double own1, double sp_ds, const double (&t)[NS], const bool (&live)[NS],
                                                 double (&r)[NS]) {
     auto value = [&](double x, double g) { return OWN ? fma(own1, x, g) : g; };
     double lo[NS], hi[NS], flo[NS], fhi[NS];
@@ -2326,40 +2335,68 @@ __device__ __forceinline__ int band_newton_rows(const SP& sp, double own1, doubl
             if (e & 1) __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // (from here on r is the trial point itself: a finished row's stays, a row stopped by the cap keeps the last one evaluated)
-    bool act[NS], any = false;
-#pragma unroll
-    for (int e = 0; e < NS; ++e) {
-        act[e] = live[e] && flo[e] * fhi[e] <= 0.0;           // (false: NaN, or no sign change within the shifts)
-        const double mid = (lo[e] + hi[e]) * 0.5;
-        double xs = lo[e] - flo[e] * band_div(hi[e] - lo[e], fhi[e] - flo[e]);      // secant start
-        xs = fhi[e] != flo[e] ? xs : mid;
-        xs = (xs > fmin(lo[e], hi[e]) && xs < fmax(lo[e], hi[e])) ? xs : mid;
-        r[e] = act[e] ? xs : r[e];
-        any = any || act[e];
-    }
-    int n = 0;
-    while (any && n < 100) {
-        ++n;
-        any = false;
+    if constexpr (BIS) {
+        bool act[NS], any = false;
 #pragma unroll
         for (int e = 0; e < NS; ++e) {
-            double g, dg;
-            sp(std::true_type(), r[e], g, dg);
-            const double f = value(r[e], g) - t[e];
-            const double ds = OWN ? fma(dg, sp_ds, own1) : dg * sp_ds;
-            const bool go = act[e] && fabs(f) > 1e-9;
-            const double l = f < 0.0 ? r[e] : lo[e], h = f < 0.0 ? hi[e] : r[e];
-            double xn = r[e] - band_div(f, ds);
-            xn = (xn > fmin(l, h) && xn < fmax(l, h)) ? xn : (l + h) * 0.5;
-            lo[e] = go ? l : lo[e]; hi[e] = go ? h : hi[e];
-            r[e] = (go && n < 100) ? xn : r[e];
-            act[e] = go;
-            any = any || go;
-            if (e & 1) __builtin_amdgcn_sched_barrier(0);
+            act[e] = live[e];
+            any = any || act[e];
         }
+        int n = 0;
+        while (any && n < 100) {
+            ++n;
+            any = false;
+#pragma unroll
+            for (int e = 0; e < NS; ++e) {
+                const double mid = (lo[e] + hi[e]) * 0.5;         // (a finished row's bracket stands: the same point again)
+                double g, d;
+                sp(std::false_type(), mid, g, d);
+                const double fm = value(mid, g) - t[e];
+                lo[e] = (act[e] && fm < 0.0) ? mid : lo[e];
+                hi[e] = (act[e] && fm > 0.0) ? mid : hi[e];
+                r[e] = act[e] ? mid : r[e];
+                act[e] = act[e] && fabs(fm) > 1e-9;
+                any = any || act[e];
+                if (e & 1) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        return n;
+    } else {
+        // (from here on r is the trial point itself: a finished row's stays, a row stopped by the cap keeps the last one evaluated)
+        bool act[NS], any = false;
+#pragma unroll
+        for (int e = 0; e < NS; ++e) {
+            act[e] = live[e] && flo[e] * fhi[e] <= 0.0;           // (false: NaN, or no sign change within the shifts)
+            const double mid = (lo[e] + hi[e]) * 0.5;
+            double xs = lo[e] - flo[e] * band_div(hi[e] - lo[e], fhi[e] - flo[e]);      // secant start
+            xs = fhi[e] != flo[e] ? xs : mid;
+            xs = (xs > fmin(lo[e], hi[e]) && xs < fmax(lo[e], hi[e])) ? xs : mid;
+            r[e] = act[e] ? xs : r[e];
+            any = any || act[e];
+        }
+        int n = 0;
+        while (any && n < 100) {
+            ++n;
+            any = false;
+#pragma unroll
+            for (int e = 0; e < NS; ++e) {
+                double g, dg;
+                sp(std::true_type(), r[e], g, dg);
+                const double f = value(r[e], g) - t[e];
+                const double ds = OWN ? fma(dg, sp_ds, own1) : dg * sp_ds;
+                const bool go = act[e] && fabs(f) > 1e-9;
+                const double l = f < 0.0 ? r[e] : lo[e], h = f < 0.0 ? hi[e] : r[e];
+                double xn = r[e] - band_div(f, ds);
+                xn = (xn > fmin(l, h) && xn < fmax(l, h)) ? xn : (l + h) * 0.5;
+                lo[e] = go ? l : lo[e]; hi[e] = go ? h : hi[e];
+                r[e] = (go && n < 100) ? xn : r[e];
+                act[e] = go;
+                any = any || go;
+                if (e & 1) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        return n;
     }
-    return n;
 }
 
 // the most trial points of the wave's rows into iters[c] (one vector atomic per wave and column; 0: nothing to record)
@@ -2375,9 +2412,10 @@ __device__ __forceinline__ void band_iters_max(int* iters, int c, int it) {
 // (its own stores, or conditioning columns) and pushes them again with the same arithmetic: a row's result does not depend on
 // the chunking.  A pair whose second row does not exist (odd N) carries its first row twice: padding never enters a search.
 // LDS: [E table: 2 x 801 | splines of the block's components, as they stand in the U section]
-// (TWIN: k_band_bisect below is this body with band_bisect_rows - a fix to tiles, `live` / `single`, staging or stores goes into both)
-template <int CLS, int LAG, bool OWN>
-__global__ __launch_bounds__(BAND_CT) void k_band_newton(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
+// BIS: the search of a step is the reference's bisection (reported as k_band_bisect; iters: midpoints), else the Newton search
+// (reported as k_band_newton; iters: trial points) - the only place the two instantiations differ.
+template <int CLS, int LAG, bool OWN, bool BIS>
+__global__ __launch_bounds__(BAND_CT) void k_band_search(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                          const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
                                                          int* __restrict__ iters, int64_t rows_per_wg, int Bc) {
     constexpr int DB = cls_db(CLS), DA = cls_da(CLS), PS = rec_stride(CLS, LAG);
@@ -2480,7 +2518,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_newton(const double* __restric
                     tg[e] = ((e & 1) ? zc[e >> 1].y : zc[e >> 1].x) - pend[e][0];
                     live[e] = full || tbase + (unsigned int)((e >> 1) * HALF + (e & 1)) < c1_32;
                 }
-                const int it = band_newton_rows<NS, OWN>(sp, own1, sp_ds, tg, live, r);
+                const int it = band_search_rows<NS, OWN, BIS>(sp, own1, sp_ds, tg, live, r);
                 // x_c is pushed on to the components that read it, and stored
 #pragma unroll
                 for (int e = 0; e < NS; ++e) band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, r[e], band_expq_far(etab, r[e], kt), pend[e]);
@@ -2508,9 +2546,10 @@ __global__ __launch_bounds__(BAND_CT) void k_band_newton(const double* __restric
 // k_band_few / k_band_few_inverse - the exp table, every spline and all columns of the tile requested together - without
 // any table; monotone part own1 x + G_c(x) (a component without a spline is linear: the first Newton step is exact).  One
 // shape per order class and record lag: groups beyond a sweep's reach are zeros in the records.
-// (TWIN: k_band_few_bisect below is this body with band_bisect_rows - a fix to tiles, staging or stores goes into both)
-template <int CLS, int LAG>
-__global__ __launch_bounds__(BAND_CT) void k_band_few_newton(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
+// BIS: the reference's bisection (reported as k_band_few_bisect; a component without a spline is bisected like any other),
+// else the Newton search (reported as k_band_few_newton) - the only place the two instantiations differ.
+template <int CLS, int LAG, bool BIS>
+__global__ __launch_bounds__(BAND_CT) void k_band_few_search(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                              const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
                                                              int* __restrict__ iters, int ntiles, int tab0, int ntab) {
     constexpr int DB = cls_db(CLS), DA = cls_da(CLS), GP = cls_gp(CLS), PS = rec_stride(CLS, LAG);
@@ -2620,351 +2659,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_newton(const double* __res
                     tg[e] = ((e & 1) ? zin[j][e >> 1].y : zin[j][e >> 1].x) - pend[e][0];
                     live[e] = tbase + (unsigned int)e < N32;
                 }
-                const int it = band_newton_rows<NS, true>(sp, own1, sp_ds, tg, live, r);
-#pragma unroll
-                for (int e = 0; e < NS; ++e) band_push_e<DB, DA, GP, LAG, true>(rec + TTM_P_HDR, start, r[e], band_expq_far(etab, r[e], kt), pend[e]);
-                char* xcol = (char*)X + (int64_t)(kcol0 + j) * ldxb;
-#pragma unroll
-                for (int q = 0; q < NP; ++q) {
-                    const unsigned int n = tbase + (unsigned int)(q * HALF);
-                    char* xp = xcol + (size_t)(n * 8u);
-                    if (n + 1 < N32) band_store2<true>(xp, r[2 * q], r[2 * q + 1]);
-                    else if (n < N32) *(double*)xp = r[2 * q];
-                }
-                band_iters_max(iters, j, it);
-            }
-        }
-        // (the searches are bound by their arithmetic, and their state leaves no registers for a second set of columns: the
-        // workgroup's next tile is requested after this one)
-        if (tile + (int)gridDim.x < ntiles) request(tile + gridDim.x, xf, zin);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// The reference's bisection in push form (root_finder = 'reference', ttm_inverse_bisect without a cap): sample_bisect
-// (csrc/ttm_eval.h) statement for statement on the rows of a thread at once, arguments as band_newton_rows.  The bracket is
-// the Newton search's, copied: [-2, 2], its ends swapped where flo > fhi, shifted by twice its width while both values lie
-// on one side of zero (at most 2000 shifts; flo = 0 or a NaN ends them).  Then midpoints only - lo = mid where fm < 0,
-// hi = mid where fm > 0, stop at !(|fm| > 1e-9) or after 100 midpoints.  There is no exit for a bracket without a sign
-// change (sample_newton has one): whatever bracket the shifts end with is bisected, and a NaN target stops at the first
-// midpoint, 0.  r: the last midpoint of a live row (a row that is not live: +2).  Returns the most midpoints a live row
-// needed.  No derivative, no division: the loop's state is lo, hi, t and r per row.
-// (The kernels below are k_band_newton / k_band_few_newton with this search in place of band_newton_rows.  One body for both
-// methods with one bracket routine was tried: it changed the register allocation of the Newton kernels - OPTLOG round 11.)
-// ---------------------------------------------------------------------------
-template <int NS, bool OWN, class SP>
-__device__ __forceinline__ int band_bisect_rows(const SP& sp, double own1, const double (&t)[NS], const bool (&live)[NS], double (&r)[NS]) {
-    auto value = [&](double x, double g) { return OWN ? fma(own1, x, g) : g; };
-    double lo[NS], hi[NS], flo[NS], fhi[NS];
-    bool widen = false;
-    {
-        double gl, gh, d;
-        sp(std::false_type(), -2.0, gl, d);                   // (the first two trial points are the same for every row)
-        sp(std::false_type(), 2.0, gh, d);
-#pragma unroll
-        for (int e = 0; e < NS; ++e) {
-            const double a = value(-2.0, gl) - t[e], b = value(2.0, gh) - t[e];
-            const bool sw = a > b;
-            flo[e] = sw ? b : a; fhi[e] = sw ? a : b;
-            lo[e] = sw ? 2.0 : -2.0; hi[e] = sw ? -2.0 : 2.0;
-            r[e] = 2.0;
-            widen = widen || (live[e] && flo[e] * fhi[e] > 0.0);
-        }
-    }
-    for (int guard = 0; guard < 2000 && widen; ++guard) {
-        widen = false;
-#pragma unroll
-        for (int e = 0; e < NS; ++e) {
-            const bool need = live[e] && flo[e] * fhi[e] > 0.0;
-            const bool sw = flo[e] > fhi[e];
-            const double l = sw ? hi[e] : lo[e], h = sw ? lo[e] : hi[e], fl = sw ? fhi[e] : flo[e], fh = sw ? flo[e] : fhi[e];
-            const double diff = h - l;
-            const bool down = fl > 0.0;                       // (need: both values on one side of zero)
-            double xt = down ? l - diff * 2.0 : h + diff * 2.0;
-            xt = need ? xt : r[e];
-            double g, d;
-            sp(std::false_type(), xt, g, d);
-            const double ft = value(xt, g) - t[e];
-            if (need) {
-                lo[e] = down ? xt : h; flo[e] = down ? ft : fh;
-                hi[e] = down ? l : xt; fhi[e] = down ? fl : ft;
-                r[e] = xt;
-            }
-            widen = widen || (need && flo[e] * fhi[e] > 0.0);
-            if (e & 1) __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    bool act[NS], any = false;
-#pragma unroll
-    for (int e = 0; e < NS; ++e) {
-        act[e] = live[e];
-        any = any || act[e];
-    }
-    int n = 0;
-    while (any && n < 100) {
-        ++n;
-        any = false;
-#pragma unroll
-        for (int e = 0; e < NS; ++e) {
-            const double mid = (lo[e] + hi[e]) * 0.5;         // (a finished row's bracket stands: the same point again)
-            double g, d;
-            sp(std::false_type(), mid, g, d);
-            const double fm = value(mid, g) - t[e];
-            lo[e] = (act[e] && fm < 0.0) ? mid : lo[e];
-            hi[e] = (act[e] && fm > 0.0) ? mid : hi[e];
-            r[e] = act[e] ? mid : r[e];
-            act[e] = act[e] && fabs(fm) > 1e-9;
-            any = any || act[e];
-            if (e & 1) __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    return n;
-}
-
-// TWIN of k_band_newton (its body, copied) with band_bisect_rows: structure, residency blocks, live / single logic and stores as
-// there - a fix goes into both; iters: midpoints
-template <int CLS, int LAG, bool OWN>
-__global__ __launch_bounds__(BAND_CT) void k_band_bisect(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
-                                                         const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
-                                                         int* __restrict__ iters, int64_t rows_per_wg, int Bc) {
-    constexpr int DB = cls_db(CLS), DA = cls_da(CLS), PS = rec_stride(CLS, LAG);
-    constexpr int NS = BAND_NS, NP = NS / 2, CT = BAND_CT, ROWS = NS * CT, HALF = 2 * CT;
-    extern __shared__ __align__(16) double g_lds[];
-    double* etab = g_lds;
-    double* tabs = g_lds + BAND_ET_DOUBLES;
-    const int tid = threadIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.x * rows_per_wg;
-    if (c0 >= N) return;
-    const int64_t c1 = c0 + rows_per_wg < N ? c0 + rows_per_wg : N;
-    const int ntile = (int)((c1 - c0 + ROWS - 1) / ROWS);
-    band_stage<false>(etab, g_band_etab, 2 * TTM_BAND_ET_N);      // (waited for with the first block's splines)
-    cdbl_p P = (cdbl_p)(U_ + p_off);
-    cdbl_p kt = (cdbl_p)g_band_taylor;
-    const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
-    const unsigned int c1_32 = (unsigned int)c1, N32 = (unsigned int)N;
-    const int64_t ldzb = ldz * 8, ldxb = ldx * 8;
-
-    for (int kb = k0; kb < k1; kb += Bc) {
-        const int ke = kb + Bc < k1 ? kb + Bc : k1;
-        __syncthreads();                                      // every wave is done with the previous block's splines
-        int tab0;
-        {
-            cint_p rb = (cint_p)(P + (int64_t)(kb + LAG) * PS), re = (cint_p)(P + (int64_t)(ke - 1 + LAG) * PS);
-            tab0 = rb[11];
-            const int n = re[11] + TTM_U_TSTRIDE * re[10] - tab0;           // doubles (even)
-            band_stage(tabs, U_ + tab0, n);
-        }
-        __syncthreads();
-        const int colb = kcol0 + (kb - k0);                   // column of component kb
-        for (int tile = 0; tile < ntile; ++tile) {
-            const unsigned int tbase = (unsigned int)c0 + (unsigned int)tile * (unsigned int)ROWS + 2u * (unsigned int)tid;
-            const bool full = c0 + (int64_t)(tile + 1) * ROWS <= c1;
-            unsigned int roff[NP];
-            bool single[NP];                                  // the pair's second row is padding
-#pragma unroll
-            for (int q = 0; q < NP; ++q) {
-                unsigned int n = tbase + (unsigned int)(q * HALF);
-                n = n < last_pair ? n : last_pair;
-                roff[q] = n * 8u;
-                single[q] = n + 1 >= N32;
-            }
-            auto load = [&](const char* col, int q) {
-                D2 v = band_load2(col + roff[q]);
-                v.y = single[q] ? v.x : v.y;
-                return v;
-            };
-            double pend[NS][LAG];
-#pragma unroll
-            for (int l = 0; l < LAG; ++l) {
-                const double s = P[(int64_t)(kb + l) * PS];
-#pragma unroll
-                for (int e = 0; e < NS; ++e) pend[e][l] = s;
-            }
-            if (colb > 0) {
-                // the LAG columns in front of the block, pushed without being solved (a column that does not exist has an
-                // all-zero record: with x = 0, E = 1 its step only shifts the sums)
-                for (int i = 0; i < LAG; ++i) {
-                    const int cc = colb - LAG + i;
-                    cdbl_p rec = P + (int64_t)(kb + i) * PS;
-                    const char* col = (const char*)X + (int64_t)(cc < 0 ? 0 : cc) * ldxb;
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) {
-                        D2 xv = load(col, q);
-                        if (cc < 0) { xv.x = 0.0; xv.y = 0.0; }
-                        band_push<DB, DA, LAG>(rec + TTM_P_HDR, rec[0], xv.x, band_expq_far(etab, xv.x, kt), pend[2 * q]);
-                        band_push<DB, DA, LAG>(rec + TTM_P_HDR, rec[0], xv.y, band_expq_far(etab, xv.y, kt), pend[2 * q + 1]);
-                    }
-                }
-            }
-            const char* zcol = (const char*)Z + (int64_t)(kb - k0) * ldzb;
-            char* xcol = (char*)X + (int64_t)colb * ldxb;
-            cdbl_p rec = P + (int64_t)(kb + LAG) * PS;
-            D2 za[NP], zb[NP];
-#pragma unroll
-            for (int q = 0; q < NP; ++q) za[q] = load(zcol, q);
-            auto step = [&](int j, const D2 (&zc)[NP], D2 (&zn)[NP]) {
-                {
-                    const char* znext = j + 1 < ke ? zcol + ldzb : zcol;      // (past the block: a harmless re-read)
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) zn[q] = load(znext, q);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const double start = rec[0], sp_a = rec[2], sp_b = rec[3], sp_ds = rec[4];
-                const double own1 = OWN ? rec[7] : 0.0;
-                cint_p ri = (cint_p)rec;
-                const int nI = ri[10];                        // (OWN: 0 - no special terms, no spline: the component is linear)
-                const double* tab = tabs + (ri[11] - tab0);
-                auto sp = [&](auto der, double x, double& g, double& dg) {
-                    if (OWN && nI <= 0) { g = 0.0; dg = 0.0; }
-                    else if (decltype(der)::value) band_spline_d(tab, nI, sp_a, sp_b, sp_ds, x, g, dg);
-                    else { g = band_spline(tab, nI, sp_a, sp_b, sp_ds, x); dg = 0.0; }
-                };
-                // (rows of the tile beyond the chunk belong to the next workgroup: not searched, not counted, not stored)
-                double tg[NS], r[NS];
-                bool live[NS];
-#pragma unroll
-                for (int e = 0; e < NS; ++e) {
-                    tg[e] = ((e & 1) ? zc[e >> 1].y : zc[e >> 1].x) - pend[e][0];
-                    live[e] = full || tbase + (unsigned int)((e >> 1) * HALF + (e & 1)) < c1_32;
-                }
-                const int it = band_bisect_rows<NS, OWN>(sp, own1, tg, live, r);
-                // x_c is pushed on to the components that read it, and stored
-#pragma unroll
-                for (int e = 0; e < NS; ++e) band_push<DB, DA, LAG>(rec + TTM_P_HDR, start, r[e], band_expq_far(etab, r[e], kt), pend[e]);
-#pragma unroll
-                for (int q = 0; q < NP; ++q) {
-                    const unsigned int n = tbase + (unsigned int)(q * HALF);
-                    char* xp = xcol + (size_t)(n * 8u);
-                    if (full || n + 1 < c1_32) band_store2<false>(xp, r[2 * q], r[2 * q + 1]);
-                    else if (n < c1_32) *(double*)xp = r[2 * q];
-                }
-                band_iters_max(iters, j - k0, it);
-                rec += PS; zcol += ldzb; xcol += ldxb;
-            };
-            int j = kb;
-            for (; j + 1 < ke; j += 2) {
-                step(j, za, zb);
-                step(j + 1, zb, za);
-            }
-            if (j < ke) step(j, za, zb);
-        }
-    }
-}
-
-// TWIN of k_band_few_newton (its body, copied) with band_bisect_rows - a fix goes into both (a component without a spline is
-// bisected like any other)
-template <int CLS, int LAG>
-__global__ __launch_bounds__(BAND_CT) void k_band_few_bisect(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
-                                                             const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
-                                                             int* __restrict__ iters, int ntiles, int tab0, int ntab) {
-    constexpr int DB = cls_db(CLS), DA = cls_da(CLS), GP = cls_gp(CLS), PS = rec_stride(CLS, LAG);
-    constexpr int NS = BAND_FEW_NS, NP = NS / 2, CT = BAND_CT, ROWS = NS * CT, HALF = 2 * CT, FD = TTM_P_FEW_D;
-    extern __shared__ __align__(16) double g_lds[];
-    double* etab = g_lds;
-    double* tabs = g_lds + BAND_ET_DOUBLES;
-    const int tid = threadIdx.x;
-    const int nc = k1 - k0;
-    cdbl_p P = (cdbl_p)(U_ + p_off);
-    cdbl_p kt = (cdbl_p)g_band_taylor;
-    const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
-    const unsigned int N32 = (unsigned int)N;
-    const int64_t ldzb = ldz * 8, ldxb = ldx * 8;
-    // the exp table and the splines: requested now, written to LDS after the first tile's columns have been requested
-    const D2 ev = *(const D2*)(g_band_etab + 2 * min(tid, TTM_BAND_ET_N - 1));
-    D2 sv[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) sv[r] = *(const D2*)(U_ + tab0 + min(2 * tid + r * 2 * CT, ntab - 2));
-    __builtin_amdgcn_sched_barrier(0);
-    // every column of a tile: the conditioning columns in front of the first component (already in X) and z; a pair whose
-    // second row is padding carries its first row twice
-    auto request = [&](int tile, D2 (&xf)[LAG][NP], D2 (&zin)[FD][NP]) {
-        unsigned int roff[NP];
-        bool single[NP];
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            unsigned int n = (unsigned int)tile * (unsigned int)ROWS + 2u * (unsigned int)tid + (unsigned int)(q * HALF);
-            n = n < last_pair ? n : last_pair;
-            roff[q] = n * 8u;
-            single[q] = n + 1 >= N32;
-        }
-        if (kcol0 > 0) {
-#pragma unroll
-            for (int i = 0; i < LAG; ++i) {
-                const int cc = kcol0 - LAG + i;
-                const char* col = (const char*)X + (int64_t)(cc < 0 ? 0 : cc) * ldxb;
-#pragma unroll
-                for (int q = 0; q < NP; ++q) { xf[i][q] = band_load2(col + roff[q]); xf[i][q].y = single[q] ? xf[i][q].x : xf[i][q].y; }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < FD; ++j) {
-            const char* col = (const char*)Z + (int64_t)min(j, nc - 1) * ldzb;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) { zin[j][q] = band_load2(col + roff[q]); zin[j][q].y = single[q] ? zin[j][q].x : zin[j][q].y; }
-        }
-    };
-    D2 xf[LAG][NP], zin[FD][NP];
-    if ((int)blockIdx.x < ntiles) request(blockIdx.x, xf, zin);
-    bool staged = false;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const unsigned int tbase = (unsigned int)tile * (unsigned int)ROWS + 2u * (unsigned int)tid;
-        __builtin_amdgcn_sched_barrier(0);
-        if (!staged) {
-            if (tid < TTM_BAND_ET_N) *(D2*)(etab + 2 * tid) = ev;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const int i = 2 * tid + r * 2 * CT;
-                if (i < ntab) *(D2*)(tabs + i) = sv[r];
-            }
-            __syncthreads();
-            staged = true;
-        }
-        double pend[NS][LAG];
-#pragma unroll
-        for (int l = 0; l < LAG; ++l) {
-            const double s0 = P[(int64_t)(k0 + l) * PS];
-#pragma unroll
-            for (int e = 0; e < NS; ++e) pend[e][l] = s0;
-        }
-        if (kcol0 > 0) {
-#pragma unroll
-            for (int i = 0; i < LAG; ++i) {
-                // (record of the column LAG - i in front of component k0; the chain it starts is component k0 + i's)
-                const bool there = kcol0 - LAG + i >= 0;
-                cdbl_p rec = P + (int64_t)(k0 + i) * PS;
-                const double start = rec[0];
-#pragma unroll
-                for (int q = 0; q < NP; ++q) {
-                    const double xa = there ? xf[i][q].x : 0.0, xb = there ? xf[i][q].y : 0.0;
-                    band_push_e<DB, DA, GP, LAG, true>(rec + TTM_P_HDR, start, xa, band_expq_far(etab, xa, kt), pend[2 * q]);
-                    band_push_e<DB, DA, GP, LAG, true>(rec + TTM_P_HDR, start, xb, band_expq_far(etab, xb, kt), pend[2 * q + 1]);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < FD; ++j) {
-            if (j < nc) {
-                cdbl_p rec = P + (int64_t)(k0 + j + LAG) * PS;
-                const double start = rec[0];                  // (of the component LAG columns on)
-                const double sp_a = rec[2], sp_b = rec[3], sp_ds = rec[4], own1 = rec[7];
-                cint_p ri = (cint_p)rec;
-                const int nI = ri[10];                        // (0: no special terms, no spline)
-                const double* tab = tabs + (ri[11] - tab0);
-                auto sp = [&](auto der, double x, double& g, double& dg) {
-                    g = 0.0; dg = 0.0;
-                    if (nI > 0) {
-                        if (decltype(der)::value) band_spline_d(tab, nI, sp_a, sp_b, sp_ds, x, g, dg);
-                        else g = band_spline(tab, nI, sp_a, sp_b, sp_ds, x);
-                    }
-                };
-                double tg[NS], r[NS];
-                bool live[NS];
-#pragma unroll
-                for (int e = 0; e < NS; ++e) {
-                    tg[e] = ((e & 1) ? zin[j][e >> 1].y : zin[j][e >> 1].x) - pend[e][0];
-                    live[e] = tbase + (unsigned int)e < N32;
-                }
-                const int it = band_bisect_rows<NS, true>(sp, own1, tg, live, r);
+                const int it = band_search_rows<NS, true, BIS>(sp, own1, sp_ds, tg, live, r);
 #pragma unroll
                 for (int e = 0; e < NS; ++e) band_push_e<DB, DA, GP, LAG, true>(rec + TTM_P_HDR, start, r[e], band_expq_far(etab, r[e], kt), pend[e]);
                 char* xcol = (char*)X + (int64_t)(kcol0 + j) * ldxb;
@@ -3172,7 +2867,7 @@ static size_t block_lds_sum(const ttm_program* p, int k0, int k1, int Bc) {
     }
     return lds;
 }
-// by SPAN, from the block's first spline to the end of its last as they stand in the U section - what k_band_newton / k_band_bisect stage
+// by SPAN, from the block's first spline to the end of its last as they stand in the U section - what k_band_search stages
 // (from its first component's offset, spline or not) and k_band_logdet (`splines_only`: from the first component that has one)
 static size_t block_lds_span(const ttm_program* p, int k0, int k1, int Bc, bool splines_only) {
     size_t lds = 0;
@@ -3296,9 +2991,9 @@ int roundtrip(const ttm_program* p, const double* U, int k0, int k1, const doubl
                   tmax, bkt, nb, slot.tab_slot, fs.ntiles, fs.tab0, fs.ntab);
 }
 
-// root search in push form, planned once for both methods (BIS: the reference's bisection, k_band_few_bisect / k_band_bisect;
-// else the Newton search, k_band_few_newton / k_band_newton); 1: not for this map / these buffers (the caller launches the
-// generic kernel)
+// root search in push form, planned once for both methods (BIS: the reference's bisection, reported as k_band_few_bisect /
+// k_band_bisect; else the Newton search, reported as k_band_few_newton / k_band_newton - instantiations of k_band_few_search /
+// k_band_search); 1: not for this map / these buffers (the caller launches the generic kernel)
 template <bool BIS>
 static int root_search(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
                        int32_t* iters, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name, bool dry = false) {
@@ -3310,10 +3005,7 @@ static int root_search(const ttm_program* p, const double* U, int k0, int k1, co
         // (a sweep that reaches further back than its records falls through to the checks of the long kernel; it does not return)
         if (fs.stageable && fs.lds <= lds_per_cu && fs.lage <= lag) {
             auto fk = with_lag(lag, [&](auto L) {
-                return with_cls<4>(cls, [&](auto C) {
-                    if constexpr (BIS) return k_band_few_bisect<decltype(C)::value, decltype(L)::value>;
-                    else return k_band_few_newton<decltype(C)::value, decltype(L)::value>;
-                });
+                return with_cls<4>(cls, [&](auto C) { return k_band_few_search<decltype(C)::value, decltype(L)::value, BIS>; });
             });
             if (dry) return 0;                                // (planned: the caller asks before it launches anything)
             return launch(fk, fs.grid, fs.lds, stream, BIS ? "k_band_few_bisect" : "k_band_few_newton", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa,
@@ -3330,10 +3022,7 @@ static int root_search(const ttm_program* p, const double* U, int k0, int k1, co
     if (dry) return 0;
     const ChunkGrid cg = chunk_grid(N, cus);
     auto kern = with_bool(sweep_has_own(p, k0, k1), [&](auto OW) {
-        return with_cls<3>(cls, [&](auto C) {
-            if constexpr (BIS) return k_band_bisect<decltype(C)::value, 2, decltype(OW)::value>;
-            else return k_band_newton<decltype(C)::value, 2, decltype(OW)::value>;
-        });
+        return with_cls<3>(cls, [&](auto C) { return k_band_search<decltype(C)::value, 2, decltype(OW)::value, BIS>; });
     });
     return launch(kern, cg.grid, lds, stream, BIS ? "k_band_bisect" : "k_band_newton", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx,
                   N, iters, cg.rows, Bc);

@@ -1479,8 +1479,8 @@ class transport_map():
         with that count as its cap, which is what the reference's
         ``while np.sum(indices) > 0`` guard (TM:3952) does to it.
         Banded separable maps with N - 1 >= NEWTON_BAND_MIN_ROWS: the rows run through the push-form bisection (k_band_bisect /
-        k_band_few_bisect; the entry point splits the call, which starts on an odd row, into its first row and the aligned
-        rest); the replay of sample 0 is the generic k_inverse_bisect's.
+        k_band_few_bisect - with k_band_newton / k_band_few_newton instantiations of one template per shape; the entry point
+        splits the call, which starts on an odd row, into its first row and the aligned rest); the replay of sample 0 is the generic k_inverse_bisect's.
         With ``root_finder = 'newton'`` (an extension, off by default): safeguarded Newton steps inside the same
         bracket and with the same stopping rule - the same roots to |S - z| <= 1e-9 in a fifth of the evaluations,
         not the reference's last midpoints and without its sample-0 quirk.  Rows are independent there: `row0` / `iters`
