@@ -560,6 +560,24 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
                        const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
                        int32_t* iters, void* stream);
 
+/* ---- score of the pullback density (no counterpart in the reference) ---------------------------------------------
+ * Gradient of log p(x) = -1/2 sum_k S_k(u)^2 + sum_k log m_k'(t_k) + const with respect to the own variables of every
+ * sample (csrc/ttm_score.h; m_k: the monotone part of component k).  Separable maps with a U-form, whole map only.
+ *   Xsoa  : the (standardised) samples the map is evaluated on, d_cols columns, column-major; conditioning columns are held
+ *           fixed and get no output
+ *   Gsoa  : Gsoa[k * ldg + n] = score of own column k of sample n (D columns)
+ *   g_scale   (nullable, D doubles): factor on the Gaussian part of column k - 1 / sigma of the column for a score in raw
+ *           coordinates; none: 1
+ *   ld_affine (nullable, 2 D doubles {scale, shift} per component): the log-determinant term is taken at
+ *           t_k = scale u_k + shift (the reference evaluates its derivative basis on the un-standardised sample,
+ *           TM:2627 / 2695: {sigma, mean} of the column); none: t = u
+ * Both matrices are read and written two rows at a time: 16-byte aligned, even leading dimensions >= N rounded up to even.
+ * Banded maps with push records run in push form (k_band_score, csrc/ttm_band.hip; option band_score = 0: the generic
+ * kernel), every other map through k_score_u, one row per thread.  TTM_E_UNSUPPORTED: the map is not separable or has no
+ * U-form; TTM_E_ARG: null or misaligned pointers, odd or short leading dimensions, N < 1 or N >= 2^28 (row offsets are 32-bit).                             */
+int ttm_score(const ttm_program* p, const double* coef, const double* fold, const double* Xsoa, int64_t ldx, int64_t N,
+              double* Gsoa, int64_t ldg, const double* g_scale, const double* ld_affine, void* stream);
+
 /* ---- K6/K7: objective + gradient reductions for optimize() -------------------------
  * integrated: TM:3300-3376 objective_function, TM:3435-3569 objective_function_jacobian
  *   out[0] = sum_n ( S^2/2 - log(r(g)+delta) ), out[1..] = sum_n d/dc of the same, [nonmon | mon]

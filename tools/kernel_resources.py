@@ -25,5 +25,6 @@ for line in out.splitlines():
         rows[cur][m.group(1)] = int(m.group(2))
 for k, v in rows.items():
     if flt in k:
-        print('%-70s vgpr %3d sgpr-spill %4d vgpr-spill %4d scratch %4d occ %d' % (k[-70:], v.get('VGPRs', -1), v.get('SGPRs Spill', -1), v.get('VGPRs Spill', -1),
-                                                                        v.get('ScratchSize [bytes/lane]', -1), v.get('Occupancy [waves/SIMD]', -1)))
+        # (lds: the STATIC bytes per workgroup; kernels that size their LDS at launch - `extern __shared__` - show what they declare beside it)
+        print('%-70s vgpr %3d sgpr-spill %4d vgpr-spill %4d scratch %4d lds %6d occ %d' % (k[-70:], v.get('VGPRs', -1), v.get('SGPRs Spill', -1), v.get('VGPRs Spill', -1),
+                                                                        v.get('ScratchSize [bytes/lane]', -1), v.get('LDS Size [bytes/block]', -1), v.get('Occupancy [waves/SIMD]', -1)))

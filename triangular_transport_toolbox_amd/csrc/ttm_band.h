@@ -62,6 +62,12 @@ int bisect(const ttm_program* p, const double* U, int k0, int k1, const double* 
 bool bisect_plans(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
                   int32_t* iters, int cus, size_t lds_per_cu, int block);
 
+// score of the pullback density of the whole map (csrc/ttm_score.h, include/ttm.h: ttm_score) in push form: one sweep over the
+// columns, G column j complete and stored at step j + lag.  g_scale / ld_affine: nullable, as ttm_score.  Planned as the long
+// kernels (a chunk of rows per workgroup, blocks of resident splines) for every map usable() accepts.  1: declined
+int score(const ttm_program* p, const double* U, const double* Xsoa, int64_t ldx, int64_t N, double* Gsoa, int64_t ldg, const double* g_scale,
+          const double* ld_affine, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name);
+
 // forward map (+ log-determinant / sum of squares) and the table inverse of the image, in ONE launch, for maps of a few components
 // (k_band_few_roundtrip): Z (nullable) = S(X), Xr = S^-1(S(X)) - conditioning columns are read from X.  Without `force` only the
 // shapes the one launch is faster for (reach <= 2 columns, no density terms); 1: declined

@@ -2680,6 +2680,268 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_search(const double* __res
 }
 
 // ---------------------------------------------------------------------------
+// score of the pullback density in push form (csrc/ttm_score.h, include/ttm.h: ttm_score):
+//
+//     G_j = -g_j sum_{l = 0..LAG} S_{j+l}(u) dS_{j+l}/du_c (u) + m_j''(t) / m_j'(t),      c the column of component j.
+//
+// One sweep over the columns, the structure of k_band_density.  At column c a row forms S_c = pend[0] + own1 x + m(x) and pushes
+// x on exactly as band_push does; the same loop over the record's groups also gives f'_{c+l, c}(x), l = 1..LAG, which wait in
+// registers (dq) until S_{c+l} is known.  S_c then closes one term of each of the LAG + 1 open score columns c - LAG .. c:
+// column c - LAG is complete and stored at step c, the last LAG columns are flushed behind the sweep.  Live per row:
+// pend[LAG], acc[LAG + 1], LAG (LAG + 1) / 2 derivatives.
+//   * the spline is gathered once for m, m', m'' (band_spline_d2: three recurrences over the six aligned 16-byte reads); with
+//     ld_affine the log-determinant term is taken at t = scale x + shift: a second gather for m'(t), m''(t) behind a uniform
+//     branch - the standardised call pays for one;
+//   * B and B' in one fused Horner pass, A' likewise next to band_push's own chain for A (band_group_d): the pushed values are
+//     band_push's, bit for bit; the groups of a record are taken one after the other for all rows, so that one group's
+//     coefficients occupy scalar registers at a time;
+//   * a non-finite sample makes every score of the row that depends on it NaN (x 0 on the constant slope of a linear own term);
+//     beyond a spline's support the tail column is exactly linear: m'' = 0.
+// Conditioning columns in front of the first component are pushed first and get no output.  With several blocks of resident
+// splines a tile walks the blocks in turn (the row state stays in registers; a single block - C5 - is staged once per launch).
+// The pair table is requested by DMA at the top and is complete behind the first stage's wait and barrier: nothing reads it before.
+// Two rows per thread for every LAG (at LAG = 2 the step is bound by its arithmetic - about twice k_band_forward's FMAs per
+// column - not by the column stream); workgroups of 1024 threads for C5's shape, of 512 for the others (band_score_ct).
+// LDS: [E table: 2 x 801 | splines of the block's components, as they stand in the U section]
+// ---------------------------------------------------------------------------
+// value (VAL), first derivative and HALF the second derivative of the spline with respect to the local coordinate
+template <bool VAL>
+__device__ __forceinline__ void band_spline_d2(const double* tab, int nI, double sp_a, double sp_b, double sp_ds, double x, double& m, double& dm,
+                                               double& hd2m) {
+    const int col = band_med3((int)fma(x, sp_b, sp_a), 0, nI - 1);
+    const double* cp = (const double*)((const char*)tab + __umul24((unsigned int)col, TTM_U_TSTRIDE * 8));
+    double c[12];
+#pragma unroll
+    for (int i = 0; i < 12; i += 2) { const D2 v = *(const D2*)(cp + i); c[i] = v.x; c[i + 1] = v.y; }
+    if (!VAL) asm volatile("" :: "v"(c[0]));                  // (keeps the six aligned 16-byte reads, see band_spline_dd)
+    const double s = fma(x, sp_ds, cp[12]);
+    // (the first two trips of the three recurrences, whose leading terms are zero, written out)
+    double a = fma(c[11], s, c[10]), da = c[11], dda = da;
+    da = fma(da, s, a);
+    a = fma(a, s, c[9]);
+#pragma unroll
+    for (int i = 8; i >= (VAL ? 0 : 1); --i) {
+        dda = fma(dda, s, da);
+        da = fma(da, s, a);
+        a = fma(a, s, c[i]);
+    }
+    if (!VAL) {
+        dda = fma(dda, s, da);
+        da = fma(da, s, a);
+    }
+    m = a; dm = da; hd2m = dda;
+}
+
+// one group of band_push with its derivative: returns base + A(x) - A[0] + E B(x) - the operations of band_push, in its order - and
+// d = f'(x) = A'(x) + E (B'(x) - x B(x) / 2), B and B' (A and A') in one fused Horner pass each.  c: B[0..DB], A[1..DA]; hx = -x / 2
+template <int DB, int DA, class C>
+__device__ __forceinline__ double band_group_d(const C c, double base, double x, double hx, double E, double& d) {
+    double b = c[DB], db = b;
+    b = fma(b, x, c[DB - 1]);
+#pragma unroll
+    for (int i = DB - 2; i >= 0; --i) {
+        db = fma(db, x, b);
+        b = fma(b, x, c[i]);
+    }
+    double a = c[DB + DA], da = a;
+#pragma unroll
+    for (int i = DA - 1; i >= 1; --i) {
+        if (i != DA - 1) da = fma(da, x, a);
+        a = fma(a, x, c[DB + i]);
+    }
+    if (DA > 1) da = fma(da, x, a);
+    a = fma(a, x, base);
+    d = fma(E, fma(hx, b, db), da);
+    return fma(E, b, a);
+}
+
+// n doubles into LDS by a workgroup of CT threads (band_stage: BAND_CT)
+template <int CT>
+__device__ __forceinline__ void band_stage_ct(double* lds_dst, const double* src, int n) {
+    const int units = n >> 1;
+    const unsigned int base = band_lds_addr(lds_dst);
+    for (int u0 = 0; u0 < units; u0 += CT) {
+        const int u = u0 + (int)threadIdx.x;
+        if (u < units) band_dma16(src + 2 * (size_t)u, __builtin_amdgcn_readfirstlane(base + (unsigned int)(u0 + ((int)threadIdx.x & ~63)) * 16u));
+    }
+}
+
+#define BAND_SCORE_NS 2
+// threads per workgroup, so that no instantiation spills: BAND_CT (128 registers per thread) holds the step of C5's shape - degree
+// class 1, two groups per record; the longer Horner chains of the other classes and the row state of the longer records (LAG = 5:
+// 52 registers per row) take half a workgroup (256 registers per thread)
+__host__ __device__ constexpr int band_score_ct(int cls, int lag) { return cls == 1 && lag == 2 ? BAND_CT : BAND_CT / 2; }
+template <int CLS, int LAG, bool OWN>
+__global__ __launch_bounds__(band_score_ct(CLS, LAG)) void k_band_score(const double* __restrict__ U_, int64_t p_off, int D, int kcol0,
+                                                        const double* __restrict__ X, int64_t ldx, int64_t N, double* __restrict__ G,
+                                                        int64_t ldg, const double* __restrict__ g_scale,
+                                                        const double* __restrict__ ld_affine, int64_t rows_per_wg, int Bc) {
+    constexpr int DB = cls_db(CLS), DA = cls_da(CLS), PS = rec_stride(CLS, LAG);
+    constexpr int NS = BAND_SCORE_NS, NP = NS / 2, CT = band_score_ct(CLS, LAG), ROWS = NS * CT, HALF = 2 * CT, NQ = LAG * (LAG + 1) / 2;
+    constexpr int GP = cls_gp(CLS);
+    extern __shared__ __align__(16) double g_lds[];
+    double* etab = g_lds;
+    double* tabs = g_lds + BAND_ET_DOUBLES;
+    const int tid = threadIdx.x;
+    const int64_t c0 = (int64_t)blockIdx.x * rows_per_wg;
+    if (c0 >= N) return;
+    const int64_t c1 = c0 + rows_per_wg < N ? c0 + rows_per_wg : N;
+    const int ntile = (int)((c1 - c0 + ROWS - 1) / ROWS);
+    band_stage_ct<CT>(etab, g_band_etab, 2 * TTM_BAND_ET_N);      // (waited for with the first block's splines)
+    cdbl_p P = (cdbl_p)(U_ + p_off);
+    cdbl_p kt = (cdbl_p)g_band_taylor;
+    cdbl_p gs = (cdbl_p)g_scale, af = (cdbl_p)ld_affine;
+    const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
+    const unsigned int c1_32 = (unsigned int)c1;
+    const int64_t ldxb = ldx * 8, ldgb = ldg * 8;
+    int tab0 = 0;
+    auto stage = [&](int kb, int ke) {                        // the splines of the components [kb, ke), as k_band_search stages them
+        cint_p rb = (cint_p)(P + (int64_t)(kb + LAG) * PS), re = (cint_p)(P + (int64_t)(ke - 1 + LAG) * PS);
+        tab0 = rb[11];
+        band_stage_ct<CT>(tabs, U_ + tab0, re[11] + TTM_U_TSTRIDE * re[10] - tab0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    const bool one = Bc >= D;                                 // one block: staged once, for every tile
+    if (one) {
+        stage(0, D);
+        __syncthreads();
+    }
+    for (int tile = 0; tile < ntile; ++tile) {
+        const unsigned int tbase = (unsigned int)c0 + (unsigned int)tile * (unsigned int)ROWS + 2u * (unsigned int)tid;
+        unsigned int roff[NP];
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            unsigned int n = tbase + (unsigned int)(q * HALF);
+            n = n < last_pair ? n : last_pair;
+            roff[q] = n * 8u;
+        }
+        // a pair of score values of column jc: rows of the tile beyond the chunk belong to the next workgroup, the second row of
+        // the last pair may not exist
+        auto store = [&](int jc, int q, double v0, double v1) {
+            const unsigned int n = tbase + (unsigned int)(q * HALF);
+            char* gp = (char*)G + (int64_t)jc * ldgb + (size_t)(n * 8u);
+            if (n + 1 < c1_32) band_store2<false>(gp, v0, v1);
+            else if (n < c1_32) *(double*)gp = v0;
+        };
+        double pend[NS][LAG], acc[NS][LAG + 1], dq[NS][NQ];  // dq[l (l - 1) / 2 + a]: f'_{., l} of a + 1 steps ago, l = 1..LAG
+#pragma unroll
+        for (int e = 0; e < NS; ++e) {
+#pragma unroll
+            for (int l = 0; l < LAG; ++l) pend[e][l] = P[(int64_t)l * PS];
+#pragma unroll
+            for (int l = 0; l <= LAG; ++l) acc[e][l] = 0.0;
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) dq[e][i] = 0.0;
+        }
+        for (int kb = 0; kb < D; kb += Bc) {
+            const int ke = kb + Bc < D ? kb + Bc : D;
+            if (!one) {
+                __syncthreads();                              // every wave is done with the previous block's splines
+                stage(kb, ke);
+                __syncthreads();
+            }
+            if (kb == 0 && kcol0 > 0) {
+                // the LAG columns in front of the first component (conditioning columns; a column that does not exist has an all-zero
+                // record: with x = 0, E = 1 its step only shifts the sums): pushed, no output.
+                // Behind the first block's barrier: band_expq reads the pair table, which every wave's DMA has to have delivered
+                for (int i = 0; i < LAG; ++i) {
+                    const int cc = kcol0 - LAG + i;
+                    cdbl_p rec = P + (int64_t)i * PS;
+                    const char* col = (const char*)X + (int64_t)(cc < 0 ? 0 : cc) * ldxb;
+#pragma unroll
+                    for (int q = 0; q < NP; ++q) {
+                        D2 xv = band_load2(col + roff[q]);
+                        if (cc < 0) { xv.x = 0.0; xv.y = 0.0; }
+                        band_push<DB, DA, LAG>(rec + TTM_P_HDR, rec[0], xv.x, band_expq(etab, xv.x, kt), pend[2 * q]);
+                        band_push<DB, DA, LAG>(rec + TTM_P_HDR, rec[0], xv.y, band_expq(etab, xv.y, kt), pend[2 * q + 1]);
+                    }
+                }
+            }
+            const char* xcol = (const char*)X + (int64_t)(kcol0 + kb) * ldxb;
+            cdbl_p rec = P + (int64_t)(kb + LAG) * PS;
+            D2 xa[NP], xb[NP];
+#pragma unroll
+            for (int q = 0; q < NP; ++q) xa[q] = band_load2(xcol + roff[q]);
+            auto step = [&](int j, const D2 (&xc)[NP], D2 (&xn)[NP]) {
+                {
+                    const char* xnext = j + 1 < ke ? xcol + ldxb : xcol;      // (past the block: a harmless re-read)
+#pragma unroll
+                    for (int q = 0; q < NP; ++q) xn[q] = band_load2(xnext + roff[q]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                const double start = rec[0], sp_a = rec[2], sp_b = rec[3], sp_ds = rec[4];
+                const double own1 = OWN ? rec[7] : 0.0;
+                const double c2 = 2.0 * (sp_ds * sp_ds);      // m'' = c2 x half the second derivative in the local coordinate
+                cint_p ri = (cint_p)rec;
+                const int nI = ri[10];                        // (0: no special terms, no spline - the component is linear)
+                const double* tab = tabs + (ri[11] - tab0);
+                double gl[LAG + 1];                           // factor on the Gaussian part of the columns j - l
+#pragma unroll
+                for (int l = 0; l <= LAG; ++l) gl[l] = gs ? gs[j - l < 0 ? 0 : j - l] : 1.0;
+                const double t_a = af ? af[2 * j] : 1.0, t_b = af ? af[2 * j + 1] : 0.0;
+                // row by row: S, which closes one term of every open column (acc[l] is column j - l), and the new column's start
+                double xr[NS], Er[NS];
+#pragma unroll
+                for (int e = 0; e < NS; ++e) {
+                    const double x = (e & 1) ? xc[e >> 1].y : xc[e >> 1].x;
+                    double m = 0.0, dm = 0.0, hd2 = 0.0;
+                    if (nI > 0) band_spline_d2<true>(tab, nI, sp_a, sp_b, sp_ds, x, m, dm, hd2);
+                    const double S = OWN ? fma(own1, x, pend[e][0] + m) : pend[e][0] + m;
+                    // m'(x); x 0: a NaN / infinite sample stays NaN beside a constant slope
+                    const double m1 = OWN ? fma(dm, sp_ds, fma(x, 0.0, own1)) : dm * sp_ds;
+                    double n1 = m1;
+                    if (af) {                                 // the log-determinant term at t: a second gather
+                        const double t = fma(t_a, x, t_b);
+                        double mt, dmt = 0.0;
+                        hd2 = 0.0;
+                        if (nI > 0) band_spline_d2<false>(tab, nI, sp_a, sp_b, sp_ds, t, mt, dmt, hd2);
+                        n1 = OWN ? fma(dmt, sp_ds, fma(t, 0.0, own1)) : dmt * sp_ds;
+                    }
+#pragma unroll
+                    for (int l = LAG; l >= 1; --l) acc[e][l] = fma(-(gl[l] * S), dq[e][l * (l - 1) / 2 + l - 1], acc[e][l - 1]);
+                    acc[e][0] = fma(-(gl[0] * S), m1, band_div(hd2 * c2, n1));
+                    xr[e] = x;
+                    Er[e] = band_expq(etab, x, kt);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int q = 0; q < NP; ++q)
+                    if (j >= LAG) store(j - LAG, q, acc[2 * q][LAG], acc[2 * q + 1][LAG]);
+                // group by group (one group's coefficients in scalar registers at a time): the pushes of band_push and the groups'
+                // derivatives, which go to the head of their queues
+#pragma unroll
+                for (int l = 0; l < LAG; ++l) {
+#pragma unroll
+                    for (int e = 0; e < NS; ++e) {
+                        double dnew;
+                        pend[e][l] = band_group_d<DB, DA>(rec + TTM_P_HDR + l * GP, l + 1 < LAG ? pend[e][l + 1] : start, xr[e], -0.5 * xr[e], Er[e], dnew);
+#pragma unroll
+                        for (int a = l; a >= 1; --a) dq[e][(l + 1) * l / 2 + a] = dq[e][(l + 1) * l / 2 + a - 1];
+                        dq[e][(l + 1) * l / 2] = dnew;
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                rec += PS; xcol += ldxb;
+            };
+            int j = kb;
+            for (; j + 1 < ke; j += 2) {
+                step(j, xa, xb);
+                step(j + 1, xb, xa);
+            }
+            if (j < ke) step(j, xa, xb);
+        }
+        // the last LAG columns: nothing beyond component D - 1 contributes
+#pragma unroll
+        for (int l = 0; l < LAG; ++l) {
+            if (D - 1 - l >= 0) {
+#pragma unroll
+                for (int q = 0; q < NP; ++q) store(D - 1 - l, q, acc[2 * q][l], acc[2 * q + 1][l]);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // TEST HOOK (ttm_math_probe, include/ttm.h): the primitives of this file on arrays, one element per thread - the pair table
 // staged by the loader of k_band_forward, the Taylor coefficients read as the kernels read them.  No map kernel calls this.
 // ---------------------------------------------------------------------------
@@ -3125,6 +3387,33 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
     auto kern = with_cls<3>(cls, [&](auto C) { return k_band_inverse<decltype(C)::value, 2, BAND_RT_KMAX>; });
     return launch(kern, cg.grid, b.lds, stream, "k_band_inverse", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, tab_x, T,
                   y_affine[0], y_affine[1], y_affine[2], tmin, tmax, bkt, nb, b.tab_slot, b.Bc, cg.rows, b.w0, b.W);
+}
+
+// score of the pullback density of the whole map in push form (k_band_score): the residency plan of the root searches, one
+// kernel body for every degree class, record lag and own-term shape; 1: not for this map / these buffers (the caller launches
+// the generic kernel)
+int score(const ttm_program* p, const double* U, const double* Xsoa, int64_t ldx, int64_t N, double* Gsoa, int64_t ldg, const double* g_scale,
+          const double* ld_affine, int cus, size_t lds_per_cu, int block, void* stream, const char** kernel_name) {
+    if (!p || !usable(p, 0, p->D) || !Xsoa || !Gsoa || N < 1 || N >= ((int64_t)1 << 28) || cus < 1) return 1;
+    if (!col_ok(Xsoa, ldx, even_rows(N)) || !col_ok(Gsoa, ldg, even_rows(N)) || !vec_ok(U)) return 1;
+    const int D = p->D, cls = p->u_h_cls, lag = p->u_p_lag, kcol0 = uc(p, 0, TTM_UC_KC);
+    const size_t fixed = (size_t)BAND_ET_DOUBLES * 8;
+    if (lds_per_cu <= fixed) return 1;
+    const int Bc = plan_blocks(p, 0, D, lds_per_cu - fixed, block);
+    if (Bc <= 0) return 1;
+    const size_t lds = block_lds_span(p, 0, D, Bc, false) + fixed;
+    if (lds > lds_per_cu) return 1;
+    const ChunkGrid cg = chunk_grid(N, cus);
+    auto kern = with_lag(lag, [&](auto L) {
+        return with_bool(sweep_has_own(p, 0, D), [&](auto OW) {
+            return with_cls<4>(cls, [&](auto C) { return k_band_score<decltype(C)::value, decltype(L)::value, decltype(OW)::value>; });
+        });
+    });
+    allow_lds((const void*)kern, lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)cg.grid), dim3(band_score_ct(cls, lag)), lds, (hipStream_t)stream, U, (int64_t)p->u_p_off, D, kcol0, Xsoa, ldx, N,
+                       Gsoa, ldg, g_scale, ld_affine, (int64_t)cg.rows, Bc);
+    if (kernel_name) *kernel_name = "k_band_score";
+    return 0;
 }
 
 int math_probe(int which, const double* a, const double* b, int64_t n, double* out, void* stream, const char** kernel_name) {

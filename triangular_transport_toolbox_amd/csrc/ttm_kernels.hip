@@ -31,6 +31,7 @@
 #include "ttm_dense.h"
 #include "ttm_rng.h"
 #include "ttm_uform.h"
+#include "ttm_score.h"
 #include "ttm_band.h"
 #include "ttm_band_image.h"
 #include "ttm_int.h"
@@ -3862,6 +3863,52 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
     hipLaunchKernelGGL(kern, dim3(grid_for(N, bd)), dim3(bd), lds_bytes(ns, bd, 0), (hipStream_t)stream, dev_prog(p), (int)k0, (int)k1,
                        coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, (const int*)nullptr);
     return check_launch("k_inverse_newton");
+}
+
+// ---------------------------------------------------------------------------
+// score of the pullback density (include/ttm.h: ttm_score; csrc/ttm_score.h)
+// ---------------------------------------------------------------------------
+struct ScoreX {
+    const double* X; int64_t ld, n;
+    __device__ double operator()(int var) const { return X[(int64_t)var * ld + n]; }
+};
+struct ScoreG {
+    double* G; int64_t ld, n;
+    __device__ void set(int k, double v) { G[(int64_t)k * ld + n] = v; }
+    __device__ void add(int k, double v) { G[(int64_t)k * ld + n] += v; }
+};
+// The generic kernel: u_score_row, one row per thread, the row's score columns accumulated in the output buffer.  Any separable
+// U-form map; what k_band_score (csrc/ttm_band.hip) is compared against.  No LDS: the splines are read where ttm_fold put them.
+__global__ __launch_bounds__(256) void k_score_u(const int* __restrict__ ucomp, const int* __restrict__ ugrp, const double* __restrict__ U,
+                                                 int D, int E, const double* __restrict__ X, int64_t ldx, int64_t N, double* G, int64_t ldg,
+                                                 const double* __restrict__ g_scale, const double* __restrict__ ld_affine) {
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+        const ScoreX xa{X, ldx, n};
+        ScoreG ga{G, ldg, n};
+        u_score_row((cint_p)ucomp, (cint_p)ugrp, (cdbl_p)U, U, D, E, xa, (cdbl_p)g_scale, (cdbl_p)ld_affine, ga);
+    }
+}
+
+int ttm_score(const ttm_program* p, const double* coef, const double* fold, const double* Xsoa, int64_t ldx, int64_t N, double* Gsoa,
+              int64_t ldg, const double* g_scale, const double* ld_affine, void* stream) {
+    int rc = validate(p, 0, p ? p->D : 0);
+    if (rc) return rc;
+    const int64_t need = (N + 1) & ~(int64_t)1;
+    auto col_ok = [&](const void* ptr, int64_t ld) { return ptr && (uintptr_t)ptr % 16 == 0 && ld % 2 == 0 && ld >= need; };
+    if (!coef || !fold || N < 1 || N >= ((int64_t)1 << 28) || !col_ok(Xsoa, ldx) || !col_ok(Gsoa, ldg) || (uintptr_t)fold % 16 != 0)
+        return set_err(TTM_E_ARG, "ttm_score: bad arguments (null or misaligned pointers, odd or short leading dimensions, N < 1)%s");
+    if (p->monotonicity != TTM_MONO_SEPARABLE || !u_on(p))
+        return set_err(TTM_E_UNSUPPORTED, "ttm_score: %s", p->monotonicity != TTM_MONO_SEPARABLE ? "the map is not separable" : "the map has no U-form");
+    const double* U = fold + fold_base_size(p);
+    if (tuning().band_score != 0 && ttm_band::usable(p, 0, p->D)) {
+        const char* name = nullptr;
+        if (ttm_band::score(p, U, Xsoa, ldx, N, Gsoa, ldg, g_scale, ld_affine, band_cus(), device_info().lds_per_cu, tuning().rt_block, stream,
+                            &name) == 0)
+            return check_launch(name);
+    }
+    hipLaunchKernelGGL(k_score_u, dim3(grid_for(N, 256)), dim3(256), 0, (hipStream_t)stream, p->ucomp, p->ugrp, U, (int)p->D,
+                       (int)(p->d_cols - p->D), Xsoa, ldx, N, Gsoa, ldg, g_scale, ld_affine);
+    return check_launch("k_score_u");
 }
 
 // workspace: [folded coefficients of the component (<= 4096) | per-block partials]

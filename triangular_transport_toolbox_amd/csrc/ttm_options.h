@@ -27,6 +27,7 @@
     X(band_ring, -1)     /* 0: banded table inverse through k_band_inverse (tables assembled per block) although images are at hand */ \
     X(band_newton, -1)   /* 0: Newton root search of banded maps through the generic k_inverse_newton instead of the push-form kernels */ \
     X(band_bisect, -1)   /* 0: bisection of banded maps (no cap) through the generic k_inverse_bisect instead of the push-form kernels */ \
+    X(band_score, -1)    /* 0: the score of banded maps (ttm_score) through the generic k_score_u instead of the push-form kernel   */ \
     X(band_resident, -1) /* cache policy of k_band_forward / k_band_inverse_ring (csrc/ttm_band_policy.h): 0 plain, 1 / 2 / 3 forward / inverse / both keep half of Z on-die */ \
     X(int_dense, -1)     /* 0: integrated maps with dense B sets through the generic kernels instead of csrc/ttm_int.hip */ \
     X(int_xprog, -1)     /* 0: integrated components without their X programs (csrc/ttm_xprog.h: forward map, objective / gradient sums); \

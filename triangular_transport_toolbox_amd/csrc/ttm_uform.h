@@ -696,3 +696,6 @@ TTM_HD int h_search(const double* xs, const int* bk, int nb, int T, double lo, d
 }
 
 }  // namespace ttm
+
+// the score of the pullback density: the per-sample routine built on the pieces above (and, in host builds, its entry point)
+#include "ttm_score.h"

@@ -1315,6 +1315,61 @@ class transport_map():
         log_ref = -0.5 * (self.D * np.log(2 * np.pi) + ss.cpu().numpy())
         return np.exp(log_ref + ld.cpu().numpy())
 
+    def _score_unsupported(self):
+        """Why this map has no device score (ttm_score: separable maps with a U-form), or None."""
+        cm = self._cm
+        if self.monotonicity.lower() != 'separable monotonicity':
+            return 'integrated-rectifier maps have no pullback density here (separable monotonicity only)'
+        if cm.u_enabled:
+            return None
+        if not cm.u_static:
+            if any(u['complex'] for u in cm.u_info):
+                return 'the map has cross terms (no univariate form)'
+            return 'the map has a polynomial order above %d (no univariate form)' % termtable.U_PMAX
+        if self._u_rejected:
+            return 'the spline fit of the special terms was rejected (fit error above the tolerance)'
+        return 'the special-term scales are too fine for a spline of %d columns' % termtable.U_NI_MAX
+
+    def score_device(self, Xs, N, coef=None, G=None, g_scale=None, ld_affine=None):
+        """Score of the pullback density for a standardised column-major device matrix Xs (d x N) -> G (D x N):
+        G[k, n] = d/du_k [ -1/2 sum_j S_j(u)^2 + sum_j log m_j'(t_j) ] of sample n, conditioning columns held fixed
+        (include/ttm.h: ttm_score).  g_scale (D, device): factor on the Gaussian part per column; ld_affine (D x 2, device,
+        {scale, shift}): the log-determinant term is taken at t_k = scale u_k + shift.  Without them: the plain score in
+        standardised coordinates.  One launch."""
+        coef = self._current(coef)
+        why = self._score_unsupported()
+        if why:
+            raise NotImplementedError('score of the pullback density: ' + why)
+        G = self._cols(self.D, N) if G is None else G
+        _capi.check(self._lib.ttm_score(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), self._ptr(Xs), Xs.shape[1], N,
+                                        self._ptr(G), G.shape[1], self._ptr(g_scale), self._ptr(ld_affine), self._stream()))
+        return G
+
+    def evaluate_pullback_score(self, X, X_star=None):
+        """Gradient of log evaluate_pullback_density(X, X_star) with respect to the raw own variables: an N x D array,
+        column k = d/dx_k.  The Gaussian part is taken at the standardised sample (factor 1 / X_std of the column), the
+        log-determinant part at the raw sample, as _log_determinant_raw(skip_in_std=False) takes it (TM:2627 / 2695).
+        Separable maps with a univariate form only."""
+        why = self._score_unsupported()
+        if why:
+            raise NotImplementedError('evaluate_pullback_score: ' + why)
+        if not self.standardize_samples:
+            # (evaluate_pullback_density then takes its Gaussian part on the training samples and its log-determinant on the given
+            # X, TM:2410-2422: what it returns is not a function of X whose gradient this could be)
+            raise NotImplementedError('evaluate_pullback_score: standardize_samples = False (the density ignores X in its Gaussian part)')
+        if X_star is not None:
+            X = np.column_stack((X_star, X))
+        X = np.asarray(X, dtype=float)
+        Xs, N = self._samples_for(X)
+        coef = self._pack_coeffs()
+        E, D = self._cm.d_cols - self.D, self.D
+        std = np.asarray(self.X_std, dtype=float)[E:E + D]
+        mean = np.asarray(self.X_mean, dtype=float)[E:E + D]
+        g_scale = self._to_dev(np.ascontiguousarray(1.0 / std))
+        ld_affine = self._to_dev(np.ascontiguousarray(np.column_stack((std, mean))))
+        G = self.score_device(Xs, N, coef, g_scale=g_scale, ld_affine=ld_affine)
+        return self._export(G, N, 0, D, False)
+
     def evaluate_pushforward_density(self, Z, log_target_pdf, X_star=None):
         """TM:2569-2644."""
         assert self.monotonicity == "separable monotonicity", \
