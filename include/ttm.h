@@ -578,6 +578,24 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
 int ttm_score(const ttm_program* p, const double* coef, const double* fold, const double* Xsoa, int64_t ldx, int64_t N,
               double* Gsoa, int64_t ldg, const double* g_scale, const double* ld_affine, void* stream);
 
+/* ---- log-density and score of an integrated-rectifier map (no counterpart in the reference) ------------------------
+ * Per sample, with c_k the own column of component k (csrc/ttm_logdensity.h):
+ *   logp[n]            = sum_k [ -1/2 S_k(u)^2 + log( (r(g_k(u)) + delta) g_scale[k] ) ]      (without the -D/2 log 2 pi)
+ *   Gsoa[k * ldg + n]  = g_scale[k] d log p / d u_ck
+ * the change-of-variables density of the map as ttm_forward evaluates it (S_k: nonmonotone sum + the Q-node quadrature sum
+ * of r(g) + delta; log(r + delta) for every rectifier) and the gradient of exactly that computed quantity with respect to
+ * the own variables - the derivative of the quadrature sum, not of the integral.  Conditioning columns are held fixed and
+ * get no output.
+ *   Xsoa    : the (standardised) samples, d_cols columns, column-major, ldx >= N
+ *   logp    : nullable, N doubles;  Gsoa : nullable, D columns, ldg >= N (one of the two at least)
+ *   g_scale : nullable, D doubles - 1 / sigma of the own columns for the density and score in raw coordinates; none: 1
+ * Rows [0, N) of the outputs are written and nothing else; no result depends on rows [N, ldx) of Xsoa.  One launch of
+ * k_logdensity_int (one row per thread, the generic table walk: the dense / X-program forms of csrc/ttm_int.hip have no part
+ * in it), graph-capturable.  TTM_E_UNSUPPORTED: the map is separable (ttm_score is for those); TTM_E_ARG: null coef / fold /
+ * Xsoa, both outputs null, N < 1, ldx < N or ldg < N; TTM_E_LIMIT: a component's three scratch sets do not fit the LDS.   */
+int ttm_logdensity(const ttm_program* p, const double* coef, const double* fold, const double* Xsoa, int64_t ldx, int64_t N,
+                   double* logp, double* Gsoa, int64_t ldg, const double* g_scale, void* stream);
+
 /* ---- K6/K7: objective + gradient reductions for optimize() -------------------------
  * integrated: TM:3300-3376 objective_function, TM:3435-3569 objective_function_jacobian
  *   out[0] = sum_n ( S^2/2 - log(r(g)+delta) ), out[1..] = sum_n d/dc of the same, [nonmon | mon]

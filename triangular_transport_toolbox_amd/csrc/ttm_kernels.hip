@@ -3911,6 +3911,55 @@ int ttm_score(const ttm_program* p, const double* coef, const double* fold, cons
     return check_launch("k_score_u");
 }
 
+// Log-density and score of an integrated-rectifier map: int_score_row (csrc/ttm_logdensity.h), one row per thread through all
+// components; the row's score columns are accumulated in the output buffer (each thread reads back what it alone wrote), the
+// log-density in a register.  No reductions, no atomics.  The generic table walk, shaped as k_objective: term tables and
+// coefficients through scalar loads, per-thread scratch columns in LDS.
+// LDS: erf table | column cache | per-thread columns [w | B values | integrals], nb1 each = the map's largest nB + 1
+__global__ __launch_bounds__(256) void k_logdensity_int(DevProg P, const double* __restrict__ coef, const double* __restrict__ fold,
+                                                        const double* __restrict__ X, int64_t ldx, int64_t N, int E, int nb1,
+                                                        double* __restrict__ logp, double* G, int64_t ldg,
+                                                        const double* __restrict__ g_scale) {
+    double* slots;
+    CacheStore<double> cst;
+    const Prog g = make_prog_lds(P, cst, slots);
+    const int bd = blockDim.x, tid = threadIdx.x;
+    LdsSlots w{slots + tid, bd};
+    LdsSlots Bv{slots + (size_t)nb1 * bd + tid, bd};
+    LdsSlots I{slots + (size_t)2 * nb1 * bd + tid, bd};
+    for (int64_t n = (int64_t)blockIdx.x * bd + tid; n < N; n += (int64_t)gridDim.x * bd) {
+        const XSoA xa{X, ldx, n};
+        VarCache<XSoA, double> x(xa, cst);
+        ScoreG ga{G, ldg, n};
+        if (G)
+            for (int k = 0; k < P.D; ++k) ga.set(k, 0.0);
+        double lp = 0.0;
+        for (int k = 0; k < P.D; ++k) {
+            const Comp c = comp_at(P, k, 0, coef, fold);
+            int_score_row(c, g, x, w, Bv, I, E, (cdbl_p)g_scale, G != nullptr, ga, lp);
+        }
+        if (logp) logp[n] = lp;
+    }
+}
+
+int ttm_logdensity(const ttm_program* p, const double* coef, const double* fold, const double* Xsoa, int64_t ldx, int64_t N,
+                   double* logp, double* Gsoa, int64_t ldg, const double* g_scale, void* stream) {
+    int rc = validate(p, 0, p ? p->D : 0);
+    if (rc) return rc;
+    if (!coef || !fold || !Xsoa || (!logp && !Gsoa) || N < 1 || ldx < N || (Gsoa && ldg < N))
+        return set_err(TTM_E_ARG, "ttm_logdensity: bad arguments (null pointers, no output, N < 1 or a leading dimension below N)%s");
+    if (p->monotonicity != TTM_MONO_INTEGRATED)
+        return set_err(TTM_E_UNSUPPORTED, "ttm_logdensity: the map is separable (ttm_score is the score of those)%s");
+    int nb1 = 1, kmax = 0;
+    for (int k = 0; k < p->D; ++k)
+        if (p->h_nb1[k] > nb1) { nb1 = p->h_nb1[k]; kmax = k; }
+    const int bd = pick_block(3 * nb1, 0);                      // per-thread scratch columns: weights, B values, integrals
+    if (!bd) return set_err(TTM_E_LIMIT, "ttm_logdensity: component %s%lld does not fit the LDS budget", "", kmax);
+    hipLaunchKernelGGL(k_logdensity_int, dim3(grid_for(N, bd)), dim3(bd), lds_bytes(3 * nb1, bd, 0), (hipStream_t)stream, dev_prog(p),
+                       coef, fold, Xsoa, ldx, N, (int)(p->d_cols - p->D), nb1, logp, Gsoa, ldg, g_scale);
+    return check_launch("k_logdensity_int");
+}
+
 // workspace: [folded coefficients of the component (<= 4096) | per-block partials]
 #define TTM_OBJ_FOLD_MAX 4096
 // (rows of per-workgroup partial sums: nout doubles, or the TTM_X_SUM_MAX sums of an X-program evaluation, csrc/ttm_xprog.h)

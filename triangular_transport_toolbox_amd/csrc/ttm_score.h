@@ -183,3 +183,6 @@ extern "C" __attribute__((used, visibility("default"))) inline int ttm_score(con
     return TTM_OK;
 }
 #endif
+
+// (the log-density and score of integrated-rectifier maps: the other half of the score, with its own host-only entry point)
+#include "ttm_logdensity.h"

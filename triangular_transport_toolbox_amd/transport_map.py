@@ -1370,6 +1370,52 @@ class transport_map():
         G = self.score_device(Xs, N, coef, g_scale=g_scale, ld_affine=ld_affine)
         return self._export(G, N, 0, D, False)
 
+    def logdensity_device(self, Xs, N, coef=None, logp=None, G=None, g_scale=None):
+        """Log-density of the pullback of an integrated-rectifier map and its score for a standardised column-major device
+        matrix Xs (d x N) -> (logp (N), G (D x N)):  logp[n] = sum_k [ -1/2 S_k(u)^2 + log((r(g_k) + delta) g_scale[k]) ] (without
+        the -D/2 log 2 pi),  G[k, n] = g_scale[k] d logp / d u_k, conditioning columns held fixed (include/ttm.h: ttm_logdensity).
+        g_scale (D, device): 1 / sigma of the own columns for raw coordinates; without it the plain density and score in
+        standardised coordinates.  Buffers given as logp / G are filled; without any, both are made.  One launch."""
+        coef = self._current(coef)
+        if self.monotonicity.lower() != 'integrated rectifier':
+            raise NotImplementedError('logdensity_device: integrated-rectifier maps only (separable maps: evaluate_pullback_density / '
+                                      'evaluate_pullback_score, score_device)')
+        if logp is None and G is None:
+            logp, G = self._empty(N), self._cols(self.D, N)
+        _capi.check(self._lib.ttm_logdensity(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), self._ptr(Xs), Xs.shape[1], N,
+                                             self._ptr(logp), self._ptr(G), G.shape[1] if G is not None else N, self._ptr(g_scale),
+                                             self._stream()))
+        return logp, G
+
+    def evaluate_pullback_logdensity(self, X, X_star=None, score=False):
+        """Log of the pullback density of an integrated-rectifier map at the raw samples X (N x D; conditioning columns X_star
+        in front, or already stacked): the change-of-variables density of the map as map() evaluates it,
+            log p(x) = -D/2 log 2 pi + sum_k [ -1/2 S_k(u)^2 + log( (r(g_k(u)) + delta) / sigma_k ) ],   u = (x - mean) / sigma.
+        score=True: also its gradient with respect to the raw own variables, an N x D array - the gradient of exactly the
+        computed quantity (the quadrature sum differentiated).  With standardize_samples=False the given X is used as it is
+        (sigma = 1).  Separable maps keep the reference's convention for the log-determinant (raw samples):
+        evaluate_pullback_density / evaluate_pullback_score are theirs."""
+        if self.monotonicity.lower() != 'integrated rectifier':
+            raise NotImplementedError('evaluate_pullback_logdensity: integrated-rectifier maps only; separable maps have '
+                                      'evaluate_pullback_density / evaluate_pullback_score (the reference\'s raw-sample log-determinant)')
+        if X_star is not None:
+            X = np.column_stack((X_star, X))
+        X = np.asarray(X, dtype=float)
+        if X.ndim != 2 or X.shape[1] != self._cm.d_cols:
+            raise ValueError('X must have shape (N, %d)' % self._cm.d_cols)
+        N = X.shape[0]
+        E, D = self._cm.d_cols - self.D, self.D
+        g_scale = None
+        if self.standardize_samples:
+            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[E:E + D]))
+        Xs = self._import(X, bool(self.standardize_samples))
+        coef = self._pack_coeffs()
+        logp, G = self.logdensity_device(Xs, N, coef, logp=self._empty(N), G=self._cols(D, N) if score else None, g_scale=g_scale)
+        logp = logp[:N].cpu().numpy() - 0.5 * D * np.log(2 * np.pi)
+        if not score:
+            return logp
+        return logp, self._export(G, N, 0, D, False)
+
     def evaluate_pushforward_density(self, Z, log_target_pdf, X_star=None):
         """TM:2569-2644."""
         assert self.monotonicity == "separable monotonicity", \
