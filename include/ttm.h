@@ -699,6 +699,23 @@ int ttm_perturb(const double* in, const double* noise, double sd, uint64_t seed,
 int ttm_map_columns(const double* in, int64_t ldi, const int32_t* src, const double* scale, const double* shift,
                     int32_t ncols, int64_t N, double* out, int64_t ldo, void* stream);
 
+/* ---- reference draws of a fitted map (no counterpart: the reference's callers draw Z on the host, example_01.py:270-273) ----
+ * Zsoa[j * ldz + n] = the standard normal deviate of draw `draw`, column col0 + j, GLOBAL row row0 + n under `seed`, for
+ * j < ncols, n < N: what ttm_inverse_table / _bisect / _newton take as Zsoa, made where they read it.  Counter-based
+ * (csrc/ttm_rng.h: normal_pair), both Box-Muller branches of one Philox-4x32-10 block for the rows 2p and 2p + 1:
+ *   r[0..3] = philox4x32_10(counter {lo32(p), hi32(p), col, 0x80000000 | draw}, key {lo32(seed), hi32(seed)})
+ *   u1, u2  = ((r[0] << 32 | r[1]) >> 11) + 0.5) 2^-53, likewise r[2], r[3]            (0 < u < 1)
+ *   row 2p <- sqrt(-2 log u1) cos(2 pi u2),   row 2p + 1 <- sqrt(-2 log u1) sin(2 pi u2)
+ * A deviate is a function of (seed, draw, column, global row) alone - not of N, of the window of rows or the columns of the
+ * call, or of the launch: ranks that shard the rows pass their offset as row0 and together draw what one rank draws.  The
+ * blocks are disjoint from ttm_perturb's (fourth counter word 0x5EED there).
+ * Rows [0, N) of every column are written and nothing else.  No alignment beyond 8 bytes, no parity requirement on row0 or
+ * ldz (a pair whose two rows lie in the window at a 16-byte aligned address is one 16-byte store, any other one or two
+ * 8-byte stores).  One launch of k_normal_fill (one thread per global row pair), no host synchronisation, graph-capturable.
+ * TTM_E_ARG: null pointer, N < 1, ncols < 1, col0 < 0, ldz < N, row0 < 0 or draw >= 2^31.                              */
+int ttm_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw,
+                    int64_t row0, void* stream);
+
 /* ---- optimisers -----------------------------------------------------------------------------------------
  * TM:3108-3114 (scipy.optimize.minimize, method 'L-BFGS-B': maxcor 10, ftol 2.22e-9, gtol 1e-5, maxls 20) as a host
  * C++ loop (csrc/ttm_lbfgsb.h: L-BFGS-B 3.0 restated, dense for the few dozen variables of a map component).

@@ -192,6 +192,7 @@ class transport_map():
             raise ValueError("root_finder must be 'reference' (TM:3798-3985, the default) or 'newton'")
         self.root_finder = root_finder
         self.objective_total = None
+        self._draws = 0                          # draw counter of reference_device / sample_device / sample
 
         X = np.asarray(X)
         if X.ndim != 2:
@@ -1439,19 +1440,7 @@ class transport_map():
         N = Z.shape[0]
         d = self._cm.d_cols
         skip = self.skip_dimensions
-        if X_star is None:
-            k0, E, Xstar_cols = 0, 0, None
-        else:
-            X_star = np.asarray(X_star, dtype=float)
-            if X_star.shape[-1] == skip:
-                k0, E, Xstar_cols = 0, skip, X_star
-            elif skip == 0:
-                E = X_star.shape[-1]
-                k0, Xstar_cols = E, X_star
-                if E + Z.shape[-1] != self.D:
-                    raise ValueError('X_star and Z must together have %d columns' % self.D)
-            else:
-                raise UnboundLocalError("local variable 'X' referenced before assignment")   # as the reference
+        k0, E, Xstar_cols = self._conditioning(X_star, Z.shape[-1])
         k1 = self.D
         ncomp = k1 - k0
         if Z.shape[-1] < ncomp:
@@ -1490,24 +1479,105 @@ class transport_map():
             if iters is not None and self.verbose and int(iters.max().item()) >= 100:
                 print('WARNING: root search stopped at maximum iterations.')
             return X[:, skip:]
-        Xs = self._cols(d, N, zero=True)
-        if Xstar_cols is not None and E > 0:
-            cols = np.array(Xstar_cols, dtype=float, copy=True)
-            if self.standardize_samples:
-                cols -= self.X_mean[:E]
-                cols /= self.X_std[:E]
-            Xs[:E, :N].copy_(torch.from_numpy(np.ascontiguousarray(cols.T)))
+        Xs = self._conditioned_cols(Xstar_cols, E, N)
         # the layout change runs on the device, into a matrix with a padded (even) leading dimension: what the large-ensemble
         # kernels need (a host transpose gave odd ensemble sizes an odd leading dimension, i.e. the generic kernel)
         Zrow = self._to_dev(np.ascontiguousarray(Z[:, :ncomp]))
         Zs = self._cols(ncomp, N)
         _capi.check(self._lib.ttm_import(self._ptr(Zrow), N, ncomp, None, None, self._ptr(Zs), Zs.shape[1], self._stream()))
+        return self._inverse_export(coef, k0, k1, Zs, Xs, N, table)
+
+    def _conditioning(self, X_star, zcols=None):
+        """(k0, E, columns): first component to invert, number of conditioning columns and their values for the three conditioning
+        shapes of TM:3639-3796; zcols: the columns of the caller's Z (None: the caller makes as many as are needed)."""
+        skip = self.skip_dimensions
+        if X_star is None:
+            return 0, 0, None
+        X_star = np.asarray(X_star, dtype=float)
+        if X_star.shape[-1] == skip:
+            return 0, skip, X_star
+        if skip == 0:
+            E = X_star.shape[-1]
+            if (E + zcols != self.D) if zcols is not None else (E >= self.D):
+                raise ValueError('X_star and Z must together have %d columns' % self.D)
+            return E, E, X_star
+        raise UnboundLocalError("local variable 'X' referenced before assignment")   # as the reference
+
+    def _conditioned_cols(self, Xstar_cols, E, N, one_point=False):
+        """The zeroed (d, ld) matrix an inverse writes into, with the standardised conditioning columns in front; one_point: the
+        single conditioning point of all N rows, spread over the rows on the device."""
+        torch = _torch()
+        Xs = self._cols(self._cm.d_cols, N, zero=True)
+        if Xstar_cols is not None and E > 0:
+            cols = np.array(Xstar_cols, dtype=float, copy=True)
+            if self.standardize_samples:
+                cols -= self.X_mean[:E]
+                cols /= self.X_std[:E]
+            if one_point:
+                Xs[:E, :N].copy_(self._to_dev(cols.reshape(E, 1)).expand(E, N))
+            else:
+                Xs[:E, :N].copy_(torch.from_numpy(np.ascontiguousarray(cols.T)))
+        return Xs
+
+    def _inverse_export(self, coef, k0, k1, Zs, Xs, N, table):
+        """The device half of inverse_map() and sample(): root searches of the components k0 .. k1 - 1 on the device matrix Zs,
+        then the layout change back (one page-locked copy) without the conditioning columns."""
         if table:
             self._inverse_table(coef, k0, k1, Zs, Xs, N)
         else:
             self._inverse_bisect(coef, k0, k1, Zs, Xs, N)
-        X = self._export(Xs, N, 0, d, self.standardize_samples)
-        return X[:, skip:]
+        X = self._export(Xs, N, 0, self._cm.d_cols, self.standardize_samples)
+        return X[:, self.skip_dimensions:]
+
+    # ---- sampling: reference draws made where the inverse reads them (no counterpart in the reference: its callers draw Z with
+    # scipy.stats.norm.rvs on the host, example_01.py:270-273, example_03.py:201-204) -----------------------------------------------------------------------
+
+    def _take_draw(self, draw):
+        """An explicit draw number as it is; None: the map's own counter, advanced - successive calls give fresh draws."""
+        if draw is None:
+            draw = self._draws
+            self._draws += 1
+        draw = int(draw)
+        if not 0 <= draw < 2 ** 31:
+            raise ValueError('draw must be in [0, 2^31)')
+        return draw
+
+    def reference_device(self, N, seed=0, draw=None, ncols=None, col0=0, row0=0, out=None):
+        """Standard normal reference draws as a column-major (ncols, ld) device matrix (ttm_normal_fill, k_normal_fill): entry
+        [j, n] is a function of (seed, draw, col0 + j, row0 + n) alone - counter-based, whatever N, the window of rows, the
+        number of columns or the launch.  ncols: by default the D columns an unconditional inverse reads; row0: the global row
+        of this rank's first row when the rows are sharded; out: a (ncols, >= N) matrix to fill instead of a new one."""
+        N = int(N)
+        ncols = self.D if ncols is None else int(ncols)
+        draw = self._take_draw(draw)
+        Z = self._cols(ncols, N) if out is None else out
+        _capi.check(self._lib.ttm_normal_fill(self._ptr(Z), Z.shape[1], N, ncols, int(col0), int(seed) % 2 ** 64, draw, int(row0),
+                                              self._stream()))
+        return Z
+
+    def sample_device(self, N, seed=0, draw=None, row0=0, X=None, Z=None):
+        """N draws from the fitted density, device-resident: reference draws (into Z, if given) pushed through the map's
+        configured inverse - inverse_device(reference_device(N, seed, draw, row0=row0), N, X=X), nothing crosses PCIe.
+        Conditioning columns (if any) must already be in X.  Returns the standardised (d, ld) matrix."""
+        Z = self.reference_device(N, seed=seed, draw=draw, row0=row0, out=Z)
+        return self.inverse_device(Z, N, X=X)
+
+    def sample(self, N, X_star=None, seed=0, draw=None, row0=0):
+        """N draws from the fitted density as an N x D NumPy array: inverse_map(Z, X_star) for the reference draws
+        Z = reference_device(N, seed, draw, ncols = components to invert, col0 = the first of them, row0), which never leave the
+        device.  X_star: the three conditioning shapes of inverse_map - component k always takes column k of the draws, so a
+        conditional draw of the components E .. D - 1 is the tail of the unconditional one - or ONE conditioning point of shape
+        (E,) / (1, E) for all N rows.  draw None: the map's own counter (a fresh draw per call); row0: as reference_device."""
+        N = int(N)
+        if N < 1:
+            raise ValueError('N must be at least 1')
+        k0, E, Xstar_cols = self._conditioning(X_star)
+        coef = self._pack_coeffs()
+        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
+        one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
+        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
+        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=self.D - k0, col0=k0, row0=row0)
+        return self._inverse_export(coef, k0, self.D, Zs, Xs, N, table)
 
     def _inverse_table(self, coef, k0, k1, Zs, Xs, N, resolution=1001, start_distance=10, row0=0):
         """TM:3987-4084 for all components: tabulate, index and look up on the device.  interp1d sorts its
