@@ -1,6 +1,6 @@
 """Time the device-resident entry points on LONG banded separable maps whose monotone parts carry a linear own term.
 
-    python tools/band_linear_bench.py [--root TREE] [--label NAME] [--commit ID] [--out FILE.json] [--launches 100] [--rounds 10]
+    python tools/band_linear_bench.py [--root TREE] [--label NAME] [--commit ID] [--out FILE.json] [--launches 100] [--rounds 10] [--rows N]
 
 Shapes: d = 40, band 2, N = 1e6 samples of specs.sample_mixture (the C5 ensemble), nonmonotone terms of C5, and as monotone
 part  (a) `linear`: [[k]] alone - the order-1 transport filter;  (b) `linear_irbf`: [k] + two iRBF - example 05's
@@ -16,14 +16,11 @@ max over the rounds), the kernel that ran (ttm_last_kernel) and the share of the
 --root: the repository tree whose package is timed (a build of another commit in a second directory: run the tool once per
 tree, one process each, in the same GPU visit and compare the files).
 """
-import argparse
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
+
+import benchlib
 
 D, BAND, N = 40, 2, 1000000
 
@@ -39,40 +36,31 @@ def spec(which):
     return mon, non
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    ap.add_argument('--label', default='')
-    ap.add_argument('--out', default='')
-    ap.add_argument('--launches', type=int, default=100)
-    ap.add_argument('--rounds', type=int, default=10)
-    ap.add_argument('--maps', default='linear,linear_irbf')
-    ap.add_argument('--rows', type=int, default=N)
-    ap.add_argument('--commit', default='', help='what to record as the commit when the tree is not a git checkout')
-    args = ap.parse_args()
-    root = os.path.abspath(args.root)
-    sys.path.insert(0, root)
-    import torch
-    import bench
-    from triangular_transport_toolbox_amd import specs
+def build(which, X):
+    """The map `which` on the ensemble X with its coefficients of the fixed seed (tools/score_bench.py times the same map)."""
     from triangular_transport_toolbox_amd.transport_map import transport_map
-    res = {'label': args.label, 'launches_per_step': args.launches, 'rounds': args.rounds, 'maps': {}}
-    try:
-        res['commit'] = subprocess.run(['git', '-C', root, 'rev-parse', '--short', 'HEAD'], capture_output=True, text=True).stdout.strip()
-    except OSError:
-        res['commit'] = ''
-    res['commit'] = args.commit or res['commit']
-    per = max(1, args.launches // args.rounds)
-    X = specs.sample_mixture(args.rows, d=D)
+    mon, non = spec(which)
+    tm = transport_map(X=X, monotone=mon, nonmonotone=non, verbose=False, monotonicity='separable monotonicity')
+    rng = np.random.default_rng(7)
+    for k in range(D):
+        tm.coeffs_mon[k] = 0.2 + 0.5 * rng.random(len(tm.coeffs_mon[k]))
+        tm.coeffs_nonmon[k] = 0.3 * rng.standard_normal(len(tm.coeffs_nonmon[k])) / (1 + np.arange(len(tm.coeffs_nonmon[k])))
+    return tm
+
+
+def main():
+    ap = benchlib.parser(__doc__, 100)
+    ap.add_argument('--maps', default='linear,linear_irbf')
+    args = ap.parse_args()
+    bench, res = benchlib.start(args, 'launches_per_step')
+    import torch
+    from triangular_transport_toolbox_amd import specs
+    res['maps'] = {}
+    X = specs.sample_mixture(args.rows or N, d=D)
     for which in args.maps.split(','):
-        mon, non = spec(which)
-        tm = transport_map(X=X, monotone=mon, nonmonotone=non, verbose=False, monotonicity='separable monotonicity')
-        rng = np.random.default_rng(7)
-        for k in range(D):
-            tm.coeffs_mon[k] = 0.2 + 0.5 * rng.random(len(tm.coeffs_mon[k]))
-            tm.coeffs_nonmon[k] = 0.3 * rng.standard_normal(len(tm.coeffs_nonmon[k])) / (1 + np.arange(len(tm.coeffs_nonmon[k])))
+        tm = build(which, X)
         lib = tm._lib
-        lib.ttm_last_kernel.restype = ctypes.c_char_p
+        kernel = benchlib.bind(lib)
         n, d = tm._N, tm._cm.d_cols
         coef = tm._pack_coeffs()
         Z = tm._cols(D, n)
@@ -86,57 +74,31 @@ def main():
             lib.ttm_inverse_newton(tm._pp, tm._ptr(coef), tm._ptr(coef._ttm_fold), 0, D, tm._ptr(Z), Z.shape[1], tm._ptr(Xinv),
                                    Xinv.shape[1], n, ctypes.c_void_p(iters.data_ptr()), tm._stream())
 
-        steps = [('forward', lambda: tm.forward_device(tm._Xs, n, coef=coef, Z=Zd), 2 * D),
-                 ('density', lambda: tm.forward_device(tm._Xs, n, coef=coef, Z=Zd, logdet=ld, sumsq=ss), 2 * D + 2),
-                 ('logdet', lambda: tm.density_device(tm._Xs, n, coef=coef, logdet=ld), D + 1),
-                 ('sumsq', lambda: tm.density_device(tm._Xs, n, coef=coef, sumsq=ss), D + 1),
-                 ('table', lambda: tm.inverse_device(Z, n, coef=coef, X=Xinv, table=True), 2 * D),
-                 ('newton', newton, 2 * D)]
-        info = {}
-        for name, fn, cols in steps:                     # warm-up of every step (tables, first launches), kernel names, errors
-            for _ in range(3):
-                fn()
-            torch.cuda.synchronize()
-            info[name] = {'kernel': lib.ttm_last_kernel().decode(), 'ms_rounds': [], 'algorithmic_gbytes': 8.0 * cols * n / 1e9}
+        steps = [('forward', None, lambda: tm.forward_device(tm._Xs, n, coef=coef, Z=Zd)),
+                 ('density', None, lambda: tm.forward_device(tm._Xs, n, coef=coef, Z=Zd, logdet=ld, sumsq=ss)),
+                 ('logdet', None, lambda: tm.density_device(tm._Xs, n, coef=coef, logdet=ld)),
+                 ('sumsq', None, lambda: tm.density_device(tm._Xs, n, coef=coef, sumsq=ss)),
+                 ('table', None, lambda: tm.inverse_device(Z, n, coef=coef, X=Xinv, table=True)),
+                 ('newton', None, newton)]
+        cols = {'forward': 2 * D, 'density': 2 * D + 2, 'logdet': D + 1, 'sumsq': D + 1, 'table': 2 * D, 'newton': 2 * D}
+
+        def after(name, v):                              # the step's algorithmic bytes, round trip and trial points of the warm-up launches
+            v['algorithmic_gbytes'] = 8.0 * cols[name] * n / 1e9
             if name in ('table', 'newton'):
-                info[name]['round_trip_max'] = float((Xinv[:, :n] - tm._Xs[:, :n]).abs().max().item())
+                v['round_trip_max'] = float((Xinv[:, :n] - tm._Xs[:, :n]).abs().max().item())
             if name == 'newton':
-                info[name]['trial_points_max_per_component'] = iters.cpu().numpy().tolist()
-        t_busy = 0.0
-        while t_busy < 1000.0:                           # keep the chip busy for a second before anything is timed
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(20):
-                steps[0][1]()
-            b.record()
-            torch.cuda.synchronize()
-            t_busy += a.elapsed_time(b)
-        for _ in range(args.rounds):
-            for name, fn, cols in steps:
-                for _ in range(2):
-                    fn()
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(per):
-                    fn()
-                b.record()
-                torch.cuda.synchronize()
-                info[name]['ms_rounds'].append(a.elapsed_time(b) / per)
-        for name, v in info.items():
-            r = np.array(v['ms_rounds'])
-            v['ms'] = float(np.median(r))
-            v['ms_min'], v['ms_max'] = float(r.min()), float(r.max())
-            v['spread_rel'] = float((r.max() - r.min()) / np.median(r))
-            v['hbm_frac_on_algorithmic_bytes'] = v['algorithmic_gbytes'] / (v['ms'] * 1e-3) / bench.HBM_PEAK_GBS
+                v['trial_points_max_per_component'] = iters.cpu().numpy().tolist()
+
+        info = benchlib.warm_up(steps, None, 3, kernel, after)
+        benchlib.keep_busy(steps[0][2], 20)
+        benchlib.time_rounds(steps, info, None, args.rounds, benchlib.per_round(args), settle=2)
+        for v in info.values():
+            benchlib.summarise(v, v['algorithmic_gbytes'], bench.HBM_PEAK_GBS)
         res['maps'][which] = {'N': n, 'D': D, 'u_p_lag': int(tm._cm.u_p_lag), 'u_h_cls': int(tm._cm.u_h_cls), 'u_h_ng': int(tm._cm.u_h_ng),
                               'steps': info}
-        print(which, json.dumps({k: (v['kernel'], round(v['ms'], 4), round(v['ms_min'], 4), round(v['ms_max'], 4)) for k, v in info.items()}), flush=True)
+        benchlib.report(which, info)
         del tm, Z, Zd, Xinv
-    print(json.dumps(res))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or '.', exist_ok=True)
-        with open(args.out, 'w') as f:
-            json.dump(res, f, indent=1)
+    benchlib.finish(res, args.out)
 
 
 if __name__ == '__main__':

@@ -12,12 +12,12 @@ the rounds of the mean forward, inverse and step time, and the rounds' min-max.
 The map, its coefficients and the buffers are bench.py's (build_map; Z and X' persist from step to step, as there).
 """
 import argparse
-import ctypes
-import json
 import os
 import sys
 
 import numpy as np
+
+import benchlib
 
 
 def main():
@@ -36,8 +36,7 @@ def main():
     def run(N, settings):
         tm, X, cfg = bench.build_map('C5', 0, n_override=N)
         lib = tm._lib
-        lib.ttm_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int32]
-        lib.ttm_last_kernel.restype = ctypes.c_char_p
+        kernel = benchlib.bind(lib)
         N, D, d = tm._N, tm.D, tm._cm.d_cols
         coef = tm._pack_coeffs()
         Xs, Z, Xinv = tm._Xs, tm._cols(D, N), tm._cols(d, N, zero=True)
@@ -52,24 +51,16 @@ def main():
             assert lib.ttm_set_option(b'band_resident', s) == 0
             tm.forward_device(Xs, N, coef=coef, Z=Z)
             torch.cuda.synchronize()
-            kf = lib.ttm_last_kernel().decode()
+            kf = kernel()
             tm.inverse_device(Z, N, coef=coef, X=Xinv)
             torch.cuda.synchronize()
-            info[s] = {'kernels': [kf, lib.ttm_last_kernel().decode()], 'fwd': [], 'inv': [], 'step': []}
+            info[s] = {'kernels': [kf, kernel()], 'fwd': [], 'inv': [], 'step': []}
             if ref is None:
                 ref = (Z.clone(), Xinv.clone())
             info[s]['bit_identical_to_first_setting'] = bool(torch.equal(Z.view(torch.int64), ref[0].view(torch.int64)) and
                                                             torch.equal(Xinv.view(torch.int64), ref[1].view(torch.int64)))
         ref = None
-        busy = 0.0
-        while busy < 1000.0:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(50):
-                step()
-            b.record()
-            torch.cuda.synchronize()
-            busy += a.elapsed_time(b)
+        benchlib.keep_busy(step, 50)
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
         for _ in range(args.rounds):
             for s in settings:
@@ -104,11 +95,7 @@ def main():
     res = {'steps_per_round': args.steps, 'rounds': args.rounds, 'halves': run(args.n, (0, 1, 2, 3)), 'sweep': []}
     for n in [int(v) for v in args.sweep.split(',') if v]:
         res['sweep'].append(run(n, (0, 3, -1)))
-    print(json.dumps(res))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or '.', exist_ok=True)
-        with open(args.out, 'w') as f:
-            json.dump(res, f, indent=1)
+    benchlib.finish(res, args.out)
 
 
 if __name__ == '__main__':

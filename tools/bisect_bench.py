@@ -1,7 +1,7 @@
 """Time the reference's bisection of the banded separable maps on the device-resident entry point (inverse_device with
 alternate_root_finding=False: the launch on rows 1.., then the replay of sample 0 with the cap, no host read between them).
 
-    python tools/bisect_bench.py [--root TREE] [--label NAME] [--commit ID] [--out FILE.json] [--launches 50] [--rounds 10]
+    python tools/bisect_bench.py [--root TREE] [--label NAME] [--commit ID] [--out FILE.json] [--launches 50] [--rounds 10] [--rows N]
 
 Workloads: C5 N = 1e6, C2b N = 1e6, C3 N = 5e5 (bench.py's maps and coefficient fixtures).  Versions, alternated round by
 round within the one process after a warm-up of every shape (the chip holds its clock only while it is kept busy: bench.py):
@@ -16,48 +16,26 @@ directory: run the tool once per tree in the same GPU visit and compare the file
 Also reported: midpoints (per-component maxima, as `iters` returns them), the kernel the launch on rows 1.. took, and - where
 the option exists - the share of entries of rows 1.. that are bit-identical under band_bisect = -1 and 0.
 """
-import argparse
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
-import numpy as np
+import benchlib
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    ap.add_argument('--label', default='')
-    ap.add_argument('--out', default='')
-    ap.add_argument('--launches', type=int, default=50)
-    ap.add_argument('--rounds', type=int, default=10)
-    ap.add_argument('--workloads', default='C5,C2b,C3')
-    ap.add_argument('--commit', default='', help='what to record as the commit when the tree is not a git checkout')
-    args = ap.parse_args()
-    root = os.path.abspath(args.root)
-    sys.path.insert(0, root)
+    args = benchlib.parser(__doc__, 50, 'C5,C2b,C3').parse_args()
+    bench, res = benchlib.start(args)
     import torch
-    import bench
-    res = {'label': args.label, 'launches_per_version': args.launches, 'rounds': args.rounds, 'workloads': {}}
-    try:
-        res['commit'] = subprocess.run(['git', '-C', root, 'rev-parse', '--short', 'HEAD'], capture_output=True, text=True).stdout.strip()
-    except OSError:
-        res['commit'] = ''
-    res['commit'] = args.commit or res['commit']
-    per = max(1, args.launches // args.rounds)
+    res['workloads'] = {}
     for wl in args.workloads.split(','):
-        tm, X, cfg = bench.build_map(wl, 0, alternate_root_finding=False)
+        tm, X, cfg = bench.build_map(wl, 0, n_override=args.rows or None, alternate_root_finding=False)
         lib = tm._lib
-        lib.ttm_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int32]
-        lib.ttm_last_kernel.restype = ctypes.c_char_p
+        kernel = benchlib.bind(lib)
         N, D, d = tm._N, tm.D, tm._cm.d_cols
         coef = tm._pack_coeffs()
         Z = tm._cols(D, N)
         tm.forward_device(tm._Xs, N, coef=coef, Z=Z)
         Xinv = tm._cols(d, N, zero=True)
-        has_opt = lib.ttm_set_option(b'band_bisect', -1) == 0
+        pin = benchlib.option(lib, 'band_bisect', probe=True)
         iters = tm._zeros(D, dtype=torch.int32)
 
         def bisect():
@@ -69,7 +47,7 @@ def main():
             lib.ttm_inverse_bisect(tm._pp, tm._ptr(coef), tm._ptr(coef._ttm_fold), 0, D, tm._ptr(Z, 1), Z.shape[1], tm._ptr(Xinv, 1),
                                    Xinv.shape[1], N - 1, ctypes.c_void_p(iters.data_ptr()), None, tm._stream())
             torch.cuda.synchronize()
-            return lib.ttm_last_kernel().decode(), iters.cpu().numpy().tolist()
+            return kernel(), iters.cpu().numpy().tolist()
 
         def newton():
             lib.ttm_inverse_newton(tm._pp, tm._ptr(coef), tm._ptr(coef._ttm_fold), 0, D, tm._ptr(Z), Z.shape[1], tm._ptr(Xinv),
@@ -78,68 +56,37 @@ def main():
         def table():
             tm.inverse_device(Z, N, coef=coef, X=Xinv, table=True)
 
-        versions = [('bisect', -1, bisect)] + ([('generic', 0, bisect)] if has_opt else []) + [('newton', -1, newton), ('table', -1, table)]
-        info, kept = {}, {}
-        for name, opt, fn in versions:                   # warm-up of every shape (tables, first launches), kernel names, errors
-            if has_opt:
-                lib.ttm_set_option(b'band_bisect', opt)
-            for _ in range(2):
-                fn()
-            torch.cuda.synchronize()
-            err = float((Xinv[:, 1:N] - tm._Xs[:, 1:N]).abs().max().item())
-            info[name] = {'round_trip_max_rows_1_on': err, 'ms_rounds': []}
-            if fn is bisect:
+        kept = {}
+
+        def after(name, v):                              # errors; for the bisection the kernel and midpoints of its launch on rows 1..
+            v['round_trip_max_rows_1_on'] = float((Xinv[:, 1:N] - tm._Xs[:, 1:N]).abs().max().item())
+            if name in ('bisect', 'generic'):
                 kept[name] = Xinv[:, 1:N].clone()
-                info[name]['kernel_rows_1_on'], info[name]['midpoints_max_per_component'] = rows_from_1()
-            else:
-                info[name]['kernel'] = lib.ttm_last_kernel().decode()
+                v['kernel'], v['midpoints_max_per_component'] = rows_from_1()
+
+        versions = [('bisect', -1, bisect)] + ([('generic', 0, bisect)] if pin else []) + [('newton', -1, newton), ('table', -1, table)]
+        info = benchlib.warm_up(versions, pin, 2, kernel, after)
         if 'generic' in kept:
             same = float((kept['bisect'] == kept['generic']).double().mean().item())
             info['bisect']['share_bit_identical_to_generic'] = same
             info['bisect']['max_abs_difference_to_generic'] = float((kept['bisect'] - kept['generic']).abs().max().item())
         kept.clear()
-        t_busy = 0.0
-        while t_busy < 1000.0:                           # keep the chip busy for a second before anything is timed
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(5):
-                versions[0][2]()
-            b.record()
-            torch.cuda.synchronize()
-            t_busy += a.elapsed_time(b)
-        for _ in range(args.rounds):
-            for name, opt, fn in versions:
-                if has_opt:
-                    lib.ttm_set_option(b'band_bisect', opt)
-                fn()
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(per):
-                    fn()
-                b.record()
-                torch.cuda.synchronize()
-                info[name]['ms_rounds'].append(a.elapsed_time(b) / per)
-        if has_opt:
-            lib.ttm_set_option(b'band_bisect', -1)
-        for name, v in info.items():
-            r = np.array(v['ms_rounds'])
-            v['ms'] = float(np.median(r))
-            v['ms_min'], v['ms_max'] = float(r.min()), float(r.max())
-            v['spread_rel'] = float((r.max() - r.min()) / np.median(r))
+        benchlib.keep_busy(versions[0][2], 5)
+        benchlib.time_rounds(versions, info, pin, args.rounds, benchlib.per_round(args), settle=1)
+        for v in info.values():
+            benchlib.summarise(v)
         out = {'N': N, 'D': D, 'versions': info}
         if 'generic' in info:
             out['generic_over_bisect'] = info['generic']['ms'] / info['bisect']['ms']
         out['bisect_over_newton'] = info['bisect']['ms'] / info['newton']['ms']
         out['bisect_over_table'] = info['bisect']['ms'] / info['table']['ms']
         res['workloads'][wl] = out
-        print(wl, json.dumps({k: (v.get('kernel_rows_1_on', v.get('kernel')), round(v['ms'], 4), round(v['ms_min'], 4), round(v['ms_max'], 4))
-                              for k, v in info.items()}), flush=True)
+        benchlib.report(wl, info)
+        for name in ('bisect', 'generic'):               # (in the file the bisection's kernel goes by what it is: that of rows 1..)
+            if name in info:
+                info[name]['kernel_rows_1_on'] = info[name].pop('kernel')
         del tm, Z, Xinv
-    print(json.dumps(res))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or '.', exist_ok=True)
-        with open(args.out, 'w') as f:
-            json.dump(res, f, indent=1)
+    benchlib.finish(res, args.out)
 
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 """Time the log-density and score of integrated-rectifier maps (ttm_logdensity) on the device-resident entry point.
 
-    python tools/logdensity_bench.py [--label NAME] [--commit ID] [--out profiles/logdensity_bench.json] [--launches 40] [--rounds 10]
+    python tools/logdensity_bench.py [--root TREE] [--rows N] [--label NAME] [--commit ID] [--out profiles/logdensity_bench.json] [--launches 40] [--rounds 10]
                                      [--workloads C2a,C5int]
 
 Workloads: C2a (spiral, d = 2, Q = 25, N = 1e6) and C5int (d = 40, band 2, Q = 25, N = 2e5) - bench.py's maps and coefficient
@@ -15,43 +15,23 @@ HIP events around every batch of launches; per version the median over the round
 max over the rounds) and the kernel that ran (ttm_last_kernel).  Derived: the ratios of `logdensity` to the two forward figures,
 and the (1 + 2 D) forward passes central finite differences of the density would cost for the same score, over `logdensity`.
 """
-import argparse
-import ctypes
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
+
+import benchlib
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--label', default='')
-    ap.add_argument('--out', default='')
-    ap.add_argument('--launches', type=int, default=40)
-    ap.add_argument('--rounds', type=int, default=10)
-    ap.add_argument('--workloads', default='C2a,C5int')
-    ap.add_argument('--rows', type=int, default=0, help='rows instead of the workload\'s own N (rehearsals)')
-    ap.add_argument('--commit', default='', help='what to record as the commit when the tree is not a git checkout')
-    args = ap.parse_args()
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, root)
+    args = benchlib.parser(__doc__, 40, 'C2a,C5int').parse_args()
+    bench, res = benchlib.start(args)
     import torch
-    import bench
     if not torch.cuda.is_available():
         raise SystemExit('logdensity_bench: no GPU - nothing is timed without one')
-    res = {'label': args.label, 'launches_per_version': args.launches, 'rounds': args.rounds, 'workloads': {}}
-    try:
-        res['commit'] = subprocess.run(['git', '-C', root, 'rev-parse', '--short', 'HEAD'], capture_output=True, text=True).stdout.strip()
-    except OSError:
-        res['commit'] = ''
-    res['commit'] = res['commit'] or args.commit
-    per = max(1, args.launches // args.rounds)
+    res['workloads'] = {}
     for wl in args.workloads.split(','):
         tm, _, _ = bench.build_map(wl, 0, n_override=args.rows or None)
         lib = tm._lib
-        lib.ttm_last_kernel.restype = ctypes.c_char_p
+        kernel = benchlib.bind(lib)
+        pin = benchlib.option(lib, 'int_dense')
         N, D, d = tm._N, tm.D, tm._cm.d_cols
         E = d - D
         coef = tm._pack_coeffs()
@@ -70,44 +50,18 @@ def main():
         def forward():
             tm.density_device(tm._Xs, N, coef=coef, logdet=ld, sigma=sg, sumsq=ss)
 
-        versions = [('logdensity', -1, logdensity), ('logp_only', -1, logp_only), ('forward', -1, forward), ('forward_generic', 0, forward)]
-        info = {}
-        for name, opt, fn in versions:                   # warm-up of every version, kernel names, the density against the forward map's
-            lib.ttm_set_option(b'int_dense', opt)
-            for _ in range(2):
-                fn()
-            torch.cuda.synchronize()
-            info[name] = {'kernel': lib.ttm_last_kernel().decode(), 'ms_rounds': []}
+        def after(name, v):                              # the density against the forward map's
             if name.startswith('forward'):
                 ref = -0.5 * ss + ld
                 fin = torch.isfinite(ref)
-                info[name]['max_rel_diff_of_logp'] = float(((lp - ref).abs() / (1.0 + ref.abs()))[fin].max().item())
-        t_busy = 0.0
-        while t_busy < 1000.0:                           # keep the chip busy for a second before anything is timed
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(4):
-                versions[0][2]()
-            b.record()
-            torch.cuda.synchronize()
-            t_busy += a.elapsed_time(b)
-        for _ in range(args.rounds):
-            for name, opt, fn in versions:
-                lib.ttm_set_option(b'int_dense', opt)
-                fn()
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(per):
-                    fn()
-                b.record()
-                torch.cuda.synchronize()
-                info[name]['ms_rounds'].append(a.elapsed_time(b) / per)
-        lib.ttm_set_option(b'int_dense', -1)
-        for name, v in info.items():
-            r = np.array(v['ms_rounds'])
-            v['ms'] = float(np.median(r))
-            v['ms_min'], v['ms_max'] = float(r.min()), float(r.max())
-            v['spread_rel'] = float((r.max() - r.min()) / np.median(r))
+                v['max_rel_diff_of_logp'] = float(((lp - ref).abs() / (1.0 + ref.abs()))[fin].max().item())
+
+        versions = [('logdensity', -1, logdensity), ('logp_only', -1, logp_only), ('forward', -1, forward), ('forward_generic', 0, forward)]
+        info = benchlib.warm_up(versions, pin, 2, kernel, after)
+        benchlib.keep_busy(versions[0][2], 4)
+        benchlib.time_rounds(versions, info, pin, args.rounds, benchlib.per_round(args), settle=1)
+        for v in info.values():
+            benchlib.summarise(v)
         t = {k: v['ms'] for k, v in info.items()}
         out = {'N': N, 'D': D, 'd': d, 'Q': int(tm._qx_d.numel()), 'versions': info,
                'logdensity_over_forward_time': t['logdensity'] / t['forward'],
@@ -119,13 +73,9 @@ def main():
                'finite_differences_over_logdensity_time': (1 + 2 * D) * t['forward'] / t['logdensity'],
                'finite_differences_generic_over_logdensity_time': (1 + 2 * D) * t['forward_generic'] / t['logdensity']}
         res['workloads'][wl] = out
-        print(wl, json.dumps({k: (v['kernel'], round(v['ms'], 4), round(v['ms_min'], 4), round(v['ms_max'], 4)) for k, v in info.items()}), flush=True)
+        benchlib.report(wl, info)
         del tm, G
-    print(json.dumps(res))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or '.', exist_ok=True)
-        with open(args.out, 'w') as f:
-            json.dump(res, f, indent=1)
+    benchlib.finish(res, args.out)
 
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 """Time sampling from a fitted map: the reference-draw fill (ttm_normal_fill), sample_device beside inverse_device, sample() beside inverse_map().
 
-    python tools/sample_bench.py [--label NAME] [--commit ID] [--out profiles/sample_bench.json] [--launches 200] [--rounds 10]
+    python tools/sample_bench.py [--root TREE] [--label NAME] [--commit ID] [--out profiles/sample_bench.json] [--launches 200] [--rounds 10]
                                  [--workloads C5,C2b,C5int] [--rows N]
 
 Workloads: C5 (d = 40, N = 1e6), C2b (d = 2, N = 1e6) and C5int (d = 40, integrated rectifier, N = 2e5: the reference's bisection
@@ -18,15 +18,12 @@ Host versions (wall clock around calls that end in a synchronise, median of --ho
   sample          sample(N): N x D NumPy array out, nothing in
   inverse_map     inverse_map(Z) on a host Z of the same size: the same array out, Z over PCIe first
 """
-import argparse
-import ctypes
 import json
-import os
-import subprocess
-import sys
 import time
 
 import numpy as np
+
+import benchlib
 
 # fp64 operations per row pair and column of k_normal_fill, counted in the ISA hipcc emits for gfx950 on the path every deviate
 # takes (the small-argument branch of sincos: 0 < t < 2 pi): 134 v_*_f64 instructions, 39 of them fused multiply-adds counted
@@ -36,33 +33,17 @@ FLOP_PER_PAIR = 134 + 39
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--label', default='')
-    ap.add_argument('--out', default='')
-    ap.add_argument('--launches', type=int, default=200)
-    ap.add_argument('--rounds', type=int, default=10)
+    ap = benchlib.parser(__doc__, 200, 'C5,C2b,C5int')
     ap.add_argument('--host-reps', type=int, default=7)
-    ap.add_argument('--workloads', default='C5,C2b,C5int')
-    ap.add_argument('--rows', type=int, default=0, help='rows instead of the workload\'s own N (rehearsals)')
-    ap.add_argument('--commit', default='', help='what to record as the commit when the tree is not a git checkout')
     args = ap.parse_args()
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, root)
+    bench, res = benchlib.start(args)
     import torch
-    import bench
     if not torch.cuda.is_available():
         raise SystemExit('sample_bench: no GPU - nothing is timed without one')
-    res = {'label': args.label, 'launches_per_version': args.launches, 'rounds': args.rounds, 'flop_per_pair': FLOP_PER_PAIR,
-           'copy_peak_GBs': bench.COPY_PEAK_GBS, 'fp64_peak_TFLOPs': bench.FP64_PEAK_TFLOPS, 'workloads': {}}
-    try:
-        res['commit'] = subprocess.run(['git', '-C', root, 'rev-parse', '--short', 'HEAD'], capture_output=True, text=True).stdout.strip()
-    except OSError:
-        res['commit'] = ''
-    res['commit'] = res['commit'] or args.commit
+    res.update({'flop_per_pair': FLOP_PER_PAIR, 'copy_peak_GBs': bench.COPY_PEAK_GBS, 'fp64_peak_TFLOPs': bench.FP64_PEAK_TFLOPS, 'workloads': {}})
     for wl in args.workloads.split(','):
         tm, _, _ = bench.build_map(wl, 0, n_override=args.rows or None)
-        lib = tm._lib
-        lib.ttm_last_kernel.restype = ctypes.c_char_p
+        kernel = benchlib.bind(tm._lib)
         N, D, d = tm._N, tm.D, tm._cm.d_cols
         coef = tm._pack_coeffs()
         Z, Zodd = tm._cols(D, N), tm._cols(D, N + 2)
@@ -81,44 +62,24 @@ def main():
         def sample_device():
             tm.sample_device(N, seed=1, draw=0, X=X, Z=Z)
 
-        versions = [('fill', fill), ('fill_odd', fill_odd), ('inverse_device', inverse_device), ('sample_device', sample_device)]
+        versions = [('fill', None, fill), ('fill_odd', None, fill_odd), ('inverse_device', None, inverse_device),
+                    ('sample_device', None, sample_device)]
         slow = tm.monotonicity.lower() != 'separable monotonicity'              # (a bisection of 2e5 x 40 roots: tens of ms)
-        per = {name: max(1, (args.launches // (20 if slow and name.endswith('device') else 1)) // args.rounds) for name, _ in versions}
-        info = {}
-        for name, fn in versions:                            # warm-up of every version, kernel names
-            for _ in range(2):
-                fn()
-            torch.cuda.synchronize()
-            info[name] = {'kernel': lib.ttm_last_kernel().decode(), 'launches_per_round': per[name], 'ms_rounds': []}
+        per = {name: max(1, (args.launches // (20 if slow and name.endswith('device') else 1)) // args.rounds) for name, _, _ in versions}
+
+        def after(name, v):
+            v['launches_per_round'] = per[name]
+
+        info = benchlib.warm_up(versions, None, 2, kernel, after)
         Xa = X[:, :N].clone()
         sample_device()
         torch.cuda.synchronize()
         info['sample_device']['equals_inverse_device_of_the_fill'] = bool(torch.equal(Xa, X[:, :N]))
         del Xa
-        t_busy = 0.0
-        while t_busy < 1000.0:                               # keep the chip busy for a second before anything is timed
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(20):
-                fill()
-            b.record()
-            torch.cuda.synchronize()
-            t_busy += a.elapsed_time(b)
-        for _ in range(args.rounds):
-            for name, fn in versions:
-                fn()
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(per[name]):
-                    fn()
-                b.record()
-                torch.cuda.synchronize()
-                info[name]['ms_rounds'].append(a.elapsed_time(b) / per[name])
-        for name, v in info.items():
-            r = np.array(v['ms_rounds'])
-            v['ms'] = float(np.median(r))
-            v['ms_min'], v['ms_max'] = float(r.min()), float(r.max())
-            v['spread_rel'] = float((r.max() - r.min()) / np.median(r))
+        benchlib.keep_busy(fill, 20)
+        benchlib.time_rounds(versions, info, None, args.rounds, per, settle=1)
+        for v in info.values():
+            benchlib.summarise(v)
         gbytes = 8.0 * N * D / 1e9
         gflop = FLOP_PER_PAIR * 0.5 * N * D / 1e9
         for name in ('fill', 'fill_odd'):
@@ -142,20 +103,17 @@ def main():
                 torch.cuda.synchronize()
                 ts.append((time.perf_counter() - t0) * 1e3)
                 assert out.shape == (N, D)
-            host[name] = {'ms': float(np.median(ts)), 'ms_min': float(min(ts)), 'ms_max': float(max(ts))}
+            h = {'ms_rounds': ts}
+            benchlib.summarise(h)
+            host[name] = {k: h[k] for k in ('ms', 'ms_min', 'ms_max')}
         t = {k: v['ms'] for k, v in info.items()}
         res['workloads'][wl] = {'N': N, 'D': D, 'd': d, 'device': info, 'host': host,
                                 'fill_over_inverse_device_time': t['fill'] / t['inverse_device'],
                                 'sample_device_over_inverse_device_time': t['sample_device'] / t['inverse_device'],
                                 'sample_over_inverse_map_time': host['sample']['ms'] / host['inverse_map']['ms']}
-        print(wl, json.dumps({k: (v['kernel'], round(v['ms'], 4), round(v['ms_min'], 4), round(v['ms_max'], 4)) for k, v in info.items()}),
-              json.dumps({k: round(v['ms'], 3) for k, v in host.items()}), flush=True)
+        benchlib.report(wl, info, json.dumps({k: round(v['ms'], 3) for k, v in host.items()}))
         del tm
-    print(json.dumps(res))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)) or '.', exist_ok=True)
-        with open(args.out, 'w') as f:
-            json.dump(res, f, indent=1)
+    benchlib.finish(res, args.out)
 
 
 if __name__ == '__main__':
