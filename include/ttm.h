@@ -716,6 +716,24 @@ int ttm_map_columns(const double* in, int64_t ldi, const int32_t* src, const dou
 int ttm_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw,
                     int64_t row0, void* stream);
 
+/* ---- quasi-Monte Carlo reference draws: Sobol' points through the normal quantile function ----------------
+ * dirs (device, ncols x 30): row j = the 30 direction numbers of column j, each < 2^30, [b] the one of index bit b; shift
+ * (device, ncols words < 2^30, or NULL for zero): the digital shift of column j.  For j < ncols, n < N, with the Gray code
+ * g = (row0 + n) ^ ((row0 + n) >> 1) of the GLOBAL row (the order of torch.quasirandom.SobolEngine):
+ *   q = shift[j] XOR (XOR over the set bits b of g of dirs[j * 30 + b])
+ *   Zsoa[j * ldz + n] = normal_quantile((q + 0.5) 2^-30)            (csrc/ttm_rng.h: AS 241 PPND16, 2^-31 <= u <= 1 - 2^-31)
+ * Which sequence, which scrambling and which dimension a column is lies in the tables alone (qmc.tables: the Joe-Kuo numbers
+ * under a linear matrix scramble).  An entry is a function of (the column's table and shift, global row) alone - not of N, of
+ * the window of rows, of the columns of the call or of the launch: ranks that shard the rows pass their offset as row0.
+ * Rows [0, N) of every column are written and nothing else.  No alignment beyond 8 bytes, no parity requirement on row0 or
+ * ldz.  One launch of k_sobol_normal_fill, no host synchronisation, graph-capturable.  The sequence has 30 index bits:
+ * row0 + N <= 2^30.
+ * TTM_E_ARG: null Zsoa or dirs, N < 1, ncols < 1, ldz < N, row0 < 0 or row0 + N > 2^30.
+ * TTM_E_LIMIT: more than 16 * 65535 = 1 048 560 columns (one launch walks at most 16 columns per workgroup row; qmc.tables
+ * ends at 21201).                                                                                                        */
+int ttm_sobol_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, const uint32_t* dirs, const uint32_t* shift,
+                          int64_t row0, void* stream);
+
 /* ---- optimisers -----------------------------------------------------------------------------------------
  * TM:3108-3114 (scipy.optimize.minimize, method 'L-BFGS-B': maxcor 10, ftol 2.22e-9, gtol 1e-5, maxls 20) as a host
  * C++ loop (csrc/ttm_lbfgsb.h: L-BFGS-B 3.0 restated, dense for the few dozen variables of a map component).

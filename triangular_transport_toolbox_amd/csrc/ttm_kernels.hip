@@ -2917,6 +2917,30 @@ __global__ __launch_bounds__(256) void k_normal_fill(double* __restrict__ Zsoa, 
     normal_fill_pair(Zsoa, ldz, N, ncols, col0, seed, draw, row0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int)blockIdx.y, (int)gridDim.y);
 }
 
+// Sobol' reference draws (ttm_sobol_normal_fill): workgroup (x, y) owns the aligned block of 1024 global rows number
+// (row0 >> 10) + x in the columns y tile .. y tile + tile - 1, thread t the rows 256 r + t of it - consecutive lanes consecutive
+// rows, a wave stores 512 contiguous bytes per column and r.  The tables are wave-uniform: the eight low direction numbers of
+// every column of the tile and the four partial points of its high Gray-code bits are staged in LDS once per workgroup, a thread
+// then forms eight conditional XORs per column and one XOR per entry (csrc/ttm_rng.h).
+__global__ __launch_bounds__(256) void k_sobol_normal_fill(double* __restrict__ Zsoa, int64_t ldz, int64_t N, int ncols, int tile,
+                                                           const uint32_t* __restrict__ dirs, const uint32_t* __restrict__ shift, int64_t row0) {
+    __shared__ uint32_t s_low[SOBOL_TILE][SOBOL_LOW], s_high[SOBOL_TILE][SOBOL_ROWS];
+    const int t = (int)threadIdx.x, j0 = (int)blockIdx.y * tile;
+    const int nc = ncols - j0 < tile ? ncols - j0 : tile;
+    const int64_t blk = (row0 >> SOBOL_SPAN) + (int64_t)blockIdx.x;
+    if (t < nc * SOBOL_LOW) {
+        s_low[t / SOBOL_LOW][t % SOBOL_LOW] = dirs[(int64_t)(j0 + t / SOBOL_LOW) * SOBOL_BITS + t % SOBOL_LOW];
+    } else if (t >= 128 && t - 128 < nc * SOBOL_ROWS) {
+        const int c = (t - 128) / SOBOL_ROWS, r = (t - 128) % SOBOL_ROWS;
+        s_high[c][r] = sobol_high(dirs + (int64_t)(j0 + c) * SOBOL_BITS, shift ? shift[j0 + c] : 0u, (uint32_t)(blk * SOBOL_ROWS + r));
+    }
+    __syncthreads();
+    for (int c = 0; c < nc; ++c)
+        sobol_fill_rows(Zsoa + (int64_t)(j0 + c) * ldz, N, row0, blk, (uint32_t)t, sobol_low(s_low[c], (uint32_t)t), s_high[c]);
+}
+static_assert(SOBOL_TILE * SOBOL_LOW <= 128 && SOBOL_TILE * SOBOL_ROWS <= 128 && (1 << SOBOL_LOW) == 256 && SOBOL_ROWS << SOBOL_LOW == 1 << SOBOL_SPAN,
+              "k_sobol_normal_fill stages its tables with the two halves of a 256-thread workgroup");
+
 // ---------------------------------------------------------------------------
 // host side: launch planning
 // ---------------------------------------------------------------------------
@@ -4324,6 +4348,21 @@ int ttm_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, int32_t
     hipLaunchKernelGGL(k_normal_fill, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, Zsoa, ldz, N, (int)ncols, (int)col0, seed,
                        draw, row0);
     return check_launch("k_normal_fill");
+}
+
+int ttm_sobol_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, const uint32_t* dirs, const uint32_t* shift, int64_t row0, void* stream) {
+    if (!sobol_fill_args_ok(Zsoa, ldz, N, ncols, dirs, row0)) return set_err(TTM_E_ARG, "ttm_sobol_normal_fill: bad arguments%s");
+    const int64_t gx = sobol_fill_blocks(N, row0);                           // <= 2^20
+    // columns per workgroup: as many (up to SOBOL_TILE) as still leave eight workgroups per CU - the staging of the tables is
+    // shared by the tile, a small grid is not worth it (OPTLOG).  The points do not depend on the tile.
+    int64_t tile = (int64_t)ncols * gx / (8 * (int64_t)device_info().cus);
+    tile = tile < 1 ? 1 : (tile > SOBOL_TILE ? SOBOL_TILE : tile);
+    if (((int64_t)ncols + tile - 1) / tile > 65535) tile = SOBOL_TILE;
+    const int64_t gy = ((int64_t)ncols + tile - 1) / tile;
+    if (gy > 65535) return set_err(TTM_E_LIMIT, "ttm_sobol_normal_fill: %s%lld columns are more than one launch covers", "", (long long)ncols);
+    hipLaunchKernelGGL(k_sobol_normal_fill, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, Zsoa, ldz, N, (int)ncols, (int)tile,
+                       dirs, shift, row0);
+    return check_launch("k_sobol_normal_fill");
 }
 
 int ttm_map_columns(const double* in, int64_t ldi, const int32_t* src, const double* scale, const double* shift, int32_t ncols,

@@ -189,7 +189,8 @@ template <int N> TTM_HD VecD<N> exp_q_tab(const double* tab, const VecD<N>& x) {
     return r;
 }
 
-TTM_HD double fast_log(double x) {
+// log(x) for a normal number x > 0 (fast_log without its rare branch: for callers whose argument cannot be anything else)
+TTM_HD double fast_log_normal(double x) {
     int e;
     double m = frexp(x, &e);                          // [0.5, 1)
     const bool small = m < 0.70710678118654752440;
@@ -206,7 +207,11 @@ TTM_HD double fast_log(double x) {
     const double R = t2 + t1;
     const double hfsq = 0.5 * f * f;
     const double dk = (double)e;
-    double res = dk * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + R) + dk * 1.90821492927058770002e-10)) - f);
+    return dk * 6.93147180369123816490e-01 - ((hfsq - (s * (hfsq + R) + dk * 1.90821492927058770002e-10)) - f);
+}
+
+TTM_HD double fast_log(double x) {
+    double res = fast_log_normal(x);
     if (!(x > 1.0e-300) || !(x < 1.0e300)) res = log(x);   // rare: 0, negative, NaN, inf, denormal range
     return res;
 }

@@ -37,7 +37,7 @@ import os
 
 import numpy as np
 
-from . import _capi, comm, lbfgsb, quantile, termtable
+from . import _capi, comm, lbfgsb, qmc, quantile, termtable
 
 __all__ = ['transport_map']
 
@@ -1542,32 +1542,51 @@ class transport_map():
             raise ValueError('draw must be in [0, 2^31)')
         return draw
 
-    def reference_device(self, N, seed=0, draw=None, ncols=None, col0=0, row0=0, out=None):
+    def reference_device(self, N, seed=0, draw=None, ncols=None, col0=0, row0=0, out=None, sequence='random', scramble=True):
         """Standard normal reference draws as a column-major (ncols, ld) device matrix (ttm_normal_fill, k_normal_fill): entry
         [j, n] is a function of (seed, draw, col0 + j, row0 + n) alone - counter-based, whatever N, the window of rows, the
         number of columns or the launch.  ncols: by default the D columns an unconditional inverse reads; row0: the global row
-        of this rank's first row when the rows are sharded; out: a (ncols, >= N) matrix to fill instead of a new one."""
+        of this rank's first row when the rows are sharded; out: a (ncols, >= N) matrix to fill instead of a new one.
+        sequence 'sobol': quasi-Monte Carlo draws instead (ttm_sobol_normal_fill, k_sobol_normal_fill) - column col0 + j is
+        Sobol' dimension col0 + j, row row0 + n its point number row0 + n, pushed through the normal quantile function;
+        `draw` selects the scrambling of (seed, draw) (qmc.tables), so successive draws are independent randomisations of the
+        one point set; scramble False: the plain sequence, seed and draw without effect.  row0 + N <= 2^30 there.  The tables of
+        a (seed, draw) are built on the host and uploaded when it is first used (10 to 40 us per column, depending on the host; the most recent few
+        are kept on the device): a new draw per call costs that on top of the launch, a repeated one does not."""
         N = int(N)
         ncols = self.D if ncols is None else int(ncols)
+        if sequence not in qmc.SEQUENCES:
+            raise ValueError('sequence must be one of %s, not %r' % (', '.join(repr(s) for s in qmc.SEQUENCES), sequence))
+        if sequence == 'sobol' and int(row0) + N > qmc.MAX_ROWS:
+            raise ValueError('a Sobol\' sequence has 2^30 points: row0 + N = %d is more' % (int(row0) + N))
         draw = self._take_draw(draw)
         Z = self._cols(ncols, N) if out is None else out
+        if sequence == 'sobol':
+            dirs, shift = qmc.device_tables(seed, draw, int(col0), ncols, scramble, Z.device)
+            _capi.check(self._lib.ttm_sobol_normal_fill(self._ptr(Z), Z.shape[1], N, ncols, ctypes.c_void_p(dirs.data_ptr()),
+                                                        ctypes.c_void_p(shift.data_ptr()), int(row0), self._stream()))
+            return Z
         _capi.check(self._lib.ttm_normal_fill(self._ptr(Z), Z.shape[1], N, ncols, int(col0), int(seed) % 2 ** 64, draw, int(row0),
                                               self._stream()))
         return Z
 
-    def sample_device(self, N, seed=0, draw=None, row0=0, X=None, Z=None):
+    def sample_device(self, N, seed=0, draw=None, row0=0, X=None, Z=None, sequence='random', scramble=True):
         """N draws from the fitted density, device-resident: reference draws (into Z, if given) pushed through the map's
         configured inverse - inverse_device(reference_device(N, seed, draw, row0=row0), N, X=X), nothing crosses PCIe.
-        Conditioning columns (if any) must already be in X.  Returns the standardised (d, ld) matrix."""
-        Z = self.reference_device(N, seed=seed, draw=draw, row0=row0, out=Z)
+        Conditioning columns (if any) must already be in X.  Returns the standardised (d, ld) matrix.  sequence, scramble:
+        as reference_device."""
+        Z = self.reference_device(N, seed=seed, draw=draw, row0=row0, out=Z, sequence=sequence, scramble=scramble)
         return self.inverse_device(Z, N, X=X)
 
-    def sample(self, N, X_star=None, seed=0, draw=None, row0=0):
+    def sample(self, N, X_star=None, seed=0, draw=None, row0=0, sequence='random', scramble=True):
         """N draws from the fitted density as an N x D NumPy array: inverse_map(Z, X_star) for the reference draws
         Z = reference_device(N, seed, draw, ncols = components to invert, col0 = the first of them, row0), which never leave the
         device.  X_star: the three conditioning shapes of inverse_map - component k always takes column k of the draws, so a
         conditional draw of the components E .. D - 1 is the tail of the unconditional one - or ONE conditioning point of shape
-        (E,) / (1, E) for all N rows.  draw None: the map's own counter (a fresh draw per call); row0: as reference_device."""
+        (E,) / (1, E) for all N rows.  draw None: the map's own counter (a fresh draw per call); row0: as reference_device.
+        sequence 'sobol' (scramble True): a randomised quasi-Monte Carlo sample - averages over it are unbiased estimates whose
+        error falls nearly as 1 / N for smooth integrands, and calls with successive draws are the independent replicates of
+        an error bar."""
         N = int(N)
         if N < 1:
             raise ValueError('N must be at least 1')
@@ -1576,7 +1595,7 @@ class transport_map():
         table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
         one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
         Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
-        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=self.D - k0, col0=k0, row0=row0)
+        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=self.D - k0, col0=k0, row0=row0, sequence=sequence, scramble=scramble)
         return self._inverse_export(coef, k0, self.D, Zs, Xs, N, table)
 
     def _inverse_table(self, coef, k0, k1, Zs, Xs, N, resolution=1001, start_distance=10, row0=0):
