@@ -472,12 +472,26 @@ int ttm_basis(const ttm_program* p, int32_t k, int32_t which, const double* Xsoa
  *   the kernels compare only the entries of the target's own bucket (k_inverse_rt) or bisect inside the buckets around
  *   it (generic kernel, which also accepts bkt[b] = searchsorted_left(tab_x, tmin + b (tmax-tmin)/nb)) - same index as
  *   the full search.
+ *   tmin / tmax are the FIRST and LAST entry of the sorted row (the clip bounds of TM:4075-4076 and the ends of the bucket
+ *   function's range), as ttm_inverse_table_index writes them.
+ *   THE TIE RULE: the located interval i = clip(searchsorted_left(tab_x, target), 1, T-1) can have tab_x[i] == tab_x[i-1] only at
+ *   i = 1 of a table with a flat start when the search is clipped (target == tab_x[0] there): interp1d's inf * 0 = NaN is an
+ *   accident of rounding, the lookup returns tab_y[i-1], the first abscissa.  The slope of a tied interval is formed with the
+ *   difference floored at 1e-300, so an UNCLIPPED search (truncate = 0) beyond a flat end returns a value of the sign of
+ *   interp1d's infinity and of magnitude above 1e250 (or that infinity).  A NaN target gives NaN.
+ *   THE ABSCISSAE: with h_y_affine every kernel - the generic one and the resident-table kernels (k_inverse_rt, k_band_inverse,
+ *   k_band_inverse_ring, k_band_few_inverse, k_band_few_roundtrip) - evaluates tab_y[i-1] = (i-1)*step + y0 and tab_y[i] (y_last at
+ *   i = T-1) in two roundings each, np.linspace's values to the bit, and forms the slope as (tab_y[i] - tab_y[i-1]) / (tab_x[i] -
+ *   tab_x[i-1]): interp1d on the rounded abscissae, not on the ideal grid (tests/test_table_lookup.py holds each kernel to that).
  *   Xsoa holds the conditioning columns on entry and receives column kc of every component.       */
 int ttm_inverse_table_build(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1,
                             const double* pts, int32_t T, double* out, void* stream);
 /* ttm_inverse_table_index: for ncomp tables (rows of tab_x, length T) compute on the device what the lookup
- * needs: tmin/tmax (np.min / np.max of the row, TM:4075-4076), the bucket index bkt (ncomp x (nb+1)) and
- * unsorted[i] = 1 when row i is not non-decreasing (then interp1d's stable sort must be applied first -
+ * needs: tmin/tmax - the first and the last entry of the row, bit for bit (np.min / np.max of a sorted row, TM:4075-4076;
+ * of tied -0.0 / 0.0 entries the one that stands first / last) -, the bucket index bkt (ncomp x (nb+1)): bkt[0] = 0,
+ * bkt[nb] = T, bkt[q] = number of entries whose bucket (ttm_inverse_table above; a scale nb / (tmax - tmin) that is 0,
+ * infinite, NaN or >= 1e300 counts as 0: every entry in bucket 0) is below q - and
+ * unsorted[i] = 1 when row i is not non-decreasing, a NaN included (then interp1d's stable sort must be applied first -
  * the host does that rare case - and tmin/tmax/bkt of that row are not valid).                          */
 int ttm_inverse_table_index(const double* tab_x, int32_t ncomp, int32_t T, int32_t nb, double* tmin, double* tmax,
                             int32_t* bkt, int32_t* unsorted, void* stream);

@@ -849,13 +849,19 @@ int ttm_inverse_table_index(const double* tab_x, int32_t ncomp, int32_t T, int32
         int bad = 0;
         for (int i = 1; i < T; ++i) bad |= !(xs[i - 1] <= xs[i]);
         tmin[c] = xs[0]; tmax[c] = xs[T - 1]; unsorted[c] = bad;
-        const double step = (xs[T - 1] - xs[0]) / (double)nb;
+        // bkt[q] = number of entries in buckets below q, the bucket function as k_table_index has it (include/ttm.h)
+        double scale = (double)nb / (xs[T - 1] - xs[0]);
+        if (!(scale > 0.0 && scale < 1.0e300)) scale = 0.0;
+        const double bias = -xs[0] * scale;
+        auto bucket = [&](double x) {
+            const double v = fma(x, scale, bias);
+            return v >= (double)(nb - 1) ? nb - 1 : (v > 0.0 ? (int)v : 0);         // (NaN: bucket 0, as the device's conversion)
+        };
         for (int q = 0; q <= nb; ++q) {
             int a = 0, b = T;
             if (q == nb) a = T;
             else if (q > 0) {
-                const double u = xs[0] + (double)q * step;
-                while (a < b) { const int mid = (a + b) >> 1; if (xs[mid] < u) a = mid + 1; else b = mid; }
+                while (a < b) { const int mid = (a + b) >> 1; if (bucket(xs[mid]) < q) a = mid + 1; else b = mid; }
             }
             bkt[(int64_t)c * (nb + 1) + q] = a;
         }
@@ -922,7 +928,7 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
                 const int i = a < 1 ? 1 : (a > T - 1 ? T - 1 : a);
                 const double y_lo = (double)(i - 1) * h_y_affine[1] + h_y_affine[0];
                 const double y_hi = (i == T - 1) ? h_y_affine[2] : (double)i * h_y_affine[1] + h_y_affine[0];
-                const double slope = fast_div(y_hi - y_lo, xs[i] - xs[i - 1]);
+                const double slope = fast_div(y_hi - y_lo, fmax(xs[i] - xs[i - 1], 1e-300));     // (tie at a flat start: table_lookup)
                 const double r = slope * (target - xs[i - 1]) + y_lo;
                 h_put(rec, st, r);
                 X[(int64_t)((const int*)rec)[3] * ldx + n] = r;

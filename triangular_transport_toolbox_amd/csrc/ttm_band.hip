@@ -1164,7 +1164,7 @@ struct BandInvCtx {
     lds_p etab1;                   // pairs {E_i, y_i}: entry i - 1 of the whole table at etab1 + 16 i
     const double* tab_x; const double* tmin; const double* tmax;
     int T, nb, tab_slot, w0, Weven, k0;
-    double y0, ystep, y0m;
+    double y0, ystep, ylast;
     int64_t ldzb, ldxb;
     unsigned int c1_32;
 };
@@ -1223,11 +1223,11 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
         band_slots<NP>([&](auto Q) { constexpr int q = decltype(Q)::value; za[q] = band_load2<band_z_nt<POL, q>>(zcol + roff[q]); });
     }
     // interp1d slope form (TM:4062-4065) in the located interval and exp(-x^2/4) = E[i-1] exp(w), w = -delta (y_lo + x) / 4
-    auto interp = [&](double y_lo, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
+    auto interp = [&](double y_lo, double y_hi, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
         const double dx = fmax(x_hi - x_lo, 1e-300);                          // (tie at a flat start: k_inverse_rt)
         double rc = __builtin_amdgcn_rcp(dx);
         rc = fma(fma(-dx, rc, 1.0), rc, rc);
-        const double delta = (ystep * rc) * (tgt - x_lo);
+        const double delta = ((y_hi - y_lo) * rc) * (tgt - x_lo);           // (the abscissae are np.linspace's to the bit: include/ttm.h)
         rr = delta + y_lo;
         const double w = (delta * -0.25) * (y_lo + rr);
         double p = fma(kt[0], w, kt[1]);
@@ -1297,18 +1297,19 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
                 for (int i = 1; i < NC; ++i) qv[e][i] = band_lds_f64_single(q4 + 8 * i);
             }
             D2 ey[NS];
-            double xlo[NS], xhi[NS];
+            double xlo[NS], xhi[NS], yhi[NS];
 #pragma unroll
             for (int e = 0; e < NS; ++e) {
 #pragma unroll
                 for (int i = 0; i < NC; ++i) pos[e] += qv[e][i] < tg[e] ? 1 : 0;
                 ey[e] = band_lds_pair(cx.etab1 + 16 * pos[e]);
+                yhi[e] = band_lds_f64_single(cx.etab1 + 16 * pos[e] + 24);    // (y of entry pos, from the pair behind; measured: a read off the pair's base register is slower)
                 const lds_p xp = xsl + 8 * pos[e];
                 xlo[e] = band_lds_f64(xp - 8);
                 xhi[e] = band_lds_f64_single(xp);
             }
 #pragma unroll
-            for (int e = 0; e < NS; ++e) interp(ey[e].y, xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
+            for (int e = 0; e < NS; ++e) interp(ey[e].y, yhi[e], xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
         };
         if (per <= 2) search(std::integral_constant<int, 2>());
         else search(std::integral_constant<int, 4>());
@@ -1329,7 +1330,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
                         if (xg[mid] < t) a = mid + 1; else b = mid;
                     }
                     const int i = min(max(a, 1), cx.T - 1);
-                    interp(fma((double)i, ystep, cx.y0m), xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + cx.y0), t, r[e], E[e]);
+                    interp((double)(i - 1) * ystep + cx.y0, i == cx.T - 1 ? cx.ylast : (double)i * ystep + cx.y0, xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + cx.y0), t, r[e], E[e]);
                 }
             }
         }
@@ -1393,18 +1394,17 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse(const double* __restri
     cdbl_p P = (cdbl_p)(U_ + p_off);
     const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
     const int64_t ldzb = ldz * 8, ldxb = ldx * 8;
-    const double y0m = y0 - ystep;
     BandInvCtx cx;
     cx.P = P; cx.kt = (cdbl_p)g_band_taylor; cx.tabs = tabs;
     cx.etab1 = band_lds(etab) - 16 * w0 - 16;
     cx.tab_x = tab_x; cx.tmin = tmin; cx.tmax = tmax;
     cx.T = T; cx.nb = nb; cx.tab_slot = tab_slot; cx.w0 = w0; cx.Weven = Weven; cx.k0 = k0;
-    cx.y0 = y0; cx.ystep = ystep; cx.y0m = y0m; cx.ldzb = ldzb; cx.ldxb = ldxb; cx.c1_32 = (unsigned int)c1;
+    cx.y0 = y0; cx.ystep = ystep; cx.ylast = ylast; cx.ldzb = ldzb; cx.ldxb = ldxb; cx.c1_32 = (unsigned int)c1;
     for (int i = tid; i < W; i += CT) {
-        // E of grid point w0 + i and, next to it, that point's abscissa exactly as the interpolation forms it from the
-        // interval number (fma(i + 1, step, y0 - step))
+        // E of grid point w0 + i and, next to it, that point's abscissa as np.linspace has it, to the bit (i * step + y0 in two
+        // roundings, the last point forced): the interpolation reads y_lo with E and y_hi from the pair behind
         etab[2 * i] = band_expq_series(w0 + i == T - 1 ? ylast : (double)(w0 + i) * ystep + y0);
-        etab[2 * i + 1] = fma((double)(w0 + i + 1), ystep, y0m);
+        etab[2 * i + 1] = w0 + i == T - 1 ? ylast : (double)(w0 + i) * ystep + y0;
     }
     double pend[NS][LAG];
 #pragma unroll
@@ -1573,13 +1573,12 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
     cdbl_p P = (cdbl_p)(U_ + p_off);
     const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
     const int64_t ldzb = ldz * 8, ldxb = ldx * 8;
-    const double y0m = y0 - ystep;
     BandInvCtx cx;
     cx.P = P; cx.kt = (cdbl_p)g_band_taylor; cx.tabs = tabs;
     cx.etab1 = band_lds(etab) - 16 * w0 - 16;
     cx.tab_x = tab_x; cx.tmin = tmin; cx.tmax = tmax;
     cx.T = T; cx.nb = nb; cx.tab_slot = tab_slot; cx.w0 = w0; cx.Weven = Weven; cx.k0 = k0;
-    cx.y0 = y0; cx.ystep = ystep; cx.y0m = y0m; cx.ldzb = ldzb; cx.ldxb = ldxb; cx.c1_32 = (unsigned int)c1;
+    cx.y0 = y0; cx.ystep = ystep; cx.ylast = ylast; cx.ldzb = ldzb; cx.ldxb = ldxb; cx.c1_32 = (unsigned int)c1;
     BandRing rg;
     {
         const int U = tab_slot >> 1, nw = (U + 63) >> 6;      // 16-byte units per image, waves that cover one
@@ -1604,7 +1603,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
     band_ring_fill(img, ncomp, tabs, tab_slot, R);
     for (int i = tid; i < W; i += CT) {
         etab[2 * i] = band_expq_series(w0 + i == T - 1 ? ylast : (double)(w0 + i) * ystep + y0);
-        etab[2 * i + 1] = fma((double)(w0 + i + 1), ystep, y0m);
+        etab[2 * i + 1] = w0 + i == T - 1 ? ylast : (double)(w0 + i) * ystep + y0;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1670,7 +1669,6 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
     const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
     const unsigned int N32 = (unsigned int)N;
     const int64_t ldzb = ldz * 8, ldxb = ldx * 8;
-    const double y0m = y0 - ystep;
     const int nb1 = nb - 1;
     // tables and bucket starts: requested now (first: the counter of outstanding loads retires in order)
     double tv[FD];
@@ -1683,11 +1681,11 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
     const int4 bv = *(const int4*)(bkt + (int64_t)bc * (nb + 1) + 4 * bw);
     __builtin_amdgcn_sched_barrier(0);
     // interp1d slope form (TM:4062-4065) in the located interval and exp(-x^2/4) = E[i-1] exp(w), w = -delta (y_lo + x) / 4
-    auto interp = [&](double y_lo, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
+    auto interp = [&](double y_lo, double y_hi, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
         const double dx = fmax(x_hi - x_lo, 1e-300);                          // (tie at a flat start: k_inverse_rt)
         double rc = __builtin_amdgcn_rcp(dx);
         rc = fma(fma(-dx, rc, 1.0), rc, rc);
-        const double delta = (ystep * rc) * (tgt - x_lo);
+        const double delta = ((y_hi - y_lo) * rc) * (tgt - x_lo);           // (the abscissae are np.linspace's to the bit: include/ttm.h)
         rr = delta + y_lo;
         const double w = (delta * -0.25) * (y_lo + rr);
         double p = fma(kt[0], w, kt[1]);
@@ -1731,11 +1729,11 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
         const unsigned int tbase = (unsigned int)tile * (unsigned int)ROWS + 2u * (unsigned int)tid;
         __builtin_amdgcn_sched_barrier(0);
         if (!staged) {
-            // E of grid point i and, next to it, that point's abscissa exactly as the interpolation forms it from the interval
-            // number (computed while the loads travel)
+            // E of grid point i and, next to it, that point's abscissa as np.linspace has it, to the bit (computed while the
+            // loads travel)
             if (tid < T) {
                 etab[2 * tid] = band_expq_series(tid == T - 1 ? ylast : (double)tid * ystep + y0);
-                etab[2 * tid + 1] = fma((double)(tid + 1), ystep, y0m);
+                etab[2 * tid + 1] = tid == T - 1 ? ylast : (double)tid * ystep + y0;
             }
             if (tid < nc) {
                 double* slot = tabs + (size_t)tid * tab_slot;
@@ -1838,17 +1836,18 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
                 }
                 {
                     D2 ey[NS];
-                    double xlo[NS], xhi[NS];
+                    double xlo[NS], xhi[NS], yhi[NS];
 #pragma unroll
                     for (int e = 0; e < NS; ++e) {
                         const int ps1 = band_med3(pos[e], 1, T - 1);          // (a flat start: the first interval, as the search in memory)
                         ey[e] = band_lds_pair(etab1 + 16 * ps1);
+                        yhi[e] = band_lds_f64_single(etab1 + 16 * ps1 + 24);
                         const lds_p xp = xsl + 8 * ps1;
                         xlo[e] = band_lds_f64(xp - 8);
                         xhi[e] = band_lds_f64_single(xp);
                     }
 #pragma unroll
-                    for (int e = 0; e < NS; ++e) interp(ey[e].y, xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
+                    for (int e = 0; e < NS; ++e) interp(ey[e].y, yhi[e], xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
                 }
                 if (outl != 0) {
                     // outliers (the tails of the table, NaN; every row of a degenerate table): clip as TM:4074-4076,
@@ -1867,7 +1866,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
                                 if (xg[mid] < t) a = mid + 1; else b = mid;
                             }
                             const int i = min(max(a, 1), T - 1);
-                            interp(fma((double)i, ystep, y0m), xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + y0), t, r[e], E[e]);
+                            interp((double)(i - 1) * ystep + y0, i == T - 1 ? ylast : (double)i * ystep + y0, xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + y0), t, r[e], E[e]);
                         }
                     }
                 }
@@ -1929,7 +1928,6 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
     const unsigned int last_pair = (unsigned int)(((N + 1) & ~(int64_t)1) - 2);
     const unsigned int N32 = (unsigned int)N;
     const int64_t ldxb = ldx * 8, ldzb = ldz * 8, ldrb = ldr * 8;
-    const double y0m = y0 - ystep;
     const int nb1 = nb - 1;
     // everything a workgroup stages, requested now
     const D2 ev = *(const D2*)(g_band_etab + 2 * min(tid, TTM_BAND_ET_N - 1));
@@ -1945,11 +1943,11 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
     const int bc = min(tid >> 8, nc - 1), bw = tid & 255;
     const int4 bv = *(const int4*)(bkt + (int64_t)bc * (nb + 1) + 4 * bw);
     __builtin_amdgcn_sched_barrier(0);
-    auto interp = [&](double y_lo, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
+    auto interp = [&](double y_lo, double y_hi, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
         const double dx = fmax(x_hi - x_lo, 1e-300);
         double rc = __builtin_amdgcn_rcp(dx);
         rc = fma(fma(-dx, rc, 1.0), rc, rc);
-        const double delta = (ystep * rc) * (tgt - x_lo);
+        const double delta = ((y_hi - y_lo) * rc) * (tgt - x_lo);           // (the abscissae are np.linspace's to the bit: include/ttm.h)
         rr = delta + y_lo;
         const double w = (delta * -0.25) * (y_lo + rr);
         double p = fma(kt[0], w, kt[1]);
@@ -2004,7 +2002,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
             }
             if (tid < T) {
                 ietab[2 * tid] = band_expq_series(tid == T - 1 ? ylast : (double)tid * ystep + y0);
-                ietab[2 * tid + 1] = fma((double)(tid + 1), ystep, y0m);
+                ietab[2 * tid + 1] = tid == T - 1 ? ylast : (double)tid * ystep + y0;
             }
             if (tid < nc) {
                 double* slot = itabs + (size_t)tid * tab_slot;
@@ -2203,17 +2201,18 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
                     }
                     {
                         D2 ey[NS];
-                        double xlo[NS], xhi[NS];
+                        double xlo[NS], xhi[NS], yhi[NS];
 #pragma unroll
                         for (int e = 0; e < NS; ++e) {
                             const int ps1 = band_med3(pos[e], 1, T - 1);
                             ey[e] = band_lds_pair(etab1 + 16 * ps1);
+                            yhi[e] = band_lds_f64_single(etab1 + 16 * ps1 + 24);
                             const lds_p xp = xsl + 8 * ps1;
                             xlo[e] = band_lds_f64(xp - 8);
                             xhi[e] = band_lds_f64_single(xp);
                         }
 #pragma unroll
-                        for (int e = 0; e < NS; ++e) interp(ey[e].y, xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
+                        for (int e = 0; e < NS; ++e) interp(ey[e].y, yhi[e], xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
                     }
                     if (outl != 0) {
                         const double* xg = tab_x + (int64_t)j * T;
@@ -2230,7 +2229,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
                                     if (xg[mid] < t) a = mid + 1; else b = mid;
                                 }
                                 const int i = min(max(a, 1), T - 1);
-                                interp(fma((double)i, ystep, y0m), xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + y0), t, r[e], E[e]);
+                                interp((double)(i - 1) * ystep + y0, i == T - 1 ? ylast : (double)i * ystep + y0, xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + y0), t, r[e], E[e]);
                             }
                         }
                     }

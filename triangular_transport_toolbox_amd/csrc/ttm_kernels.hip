@@ -1501,10 +1501,10 @@ __global__ __launch_bounds__(1024) void k_inverse_rt(const int* __restrict__ uco
     const unsigned int row0 = (unsigned int)c0 + 2u * (unsigned int)tid, c1_32 = (unsigned int)c1;
     if (ETAB)
         for (int i = tid; i < W; i += CT) {
-            // E of grid point w0 + i and, next to it, that point's abscissa exactly as the interpolation forms it from the
-            // interval number (fma(i + 1, step, y0 - step)): one 16-byte read per row instead of a read, a convert and an fma
+            // E of grid point w0 + i and, next to it, that point's abscissa as np.linspace has it, to the bit (i * step + y0 in
+            // two roundings, the last point forced): y_lo comes with E in one 16-byte read per row, y_hi from the pair behind
             etab[2 * i] = exp_q_fast(w0 + i == T - 1 ? ylast : (double)(w0 + i) * ystep + y0);
-            etab[2 * i + 1] = fma((double)(w0 + i + 1), ystep, y0 - ystep);
+            etab[2 * i + 1] = w0 + i == T - 1 ? ylast : (double)(w0 + i) * ystep + y0;
         }
     // Taylor coefficients 1/7! .. 1/2! of the ETAB put, kept in VGPRs (as scalars they would push the kernel over the
     // SGPR budget and be spilled to VGPR lanes: v_readlane + hazard nops in the middle of every step)
@@ -1518,7 +1518,6 @@ __global__ __launch_bounds__(1024) void k_inverse_rt(const int* __restrict__ uco
         }
     }
     const int64_t ldzb = ldz * 8, ldxb = ldx * 8;
-    const double y0m = y0 - ystep;
     const int kc_first = ((cint_p)ucomp_)[k0 * TTM_UC_LEN + TTM_UC_KC];    // BAND: column of component k is kc_first + k - k0
     D2 bx1[NP], be1[NP], bx2[NP], be2[NP];                               // BAND: x and exp(-x^2/4) of columns kc-1 and kc-2
 #pragma unroll
@@ -1792,15 +1791,15 @@ __global__ __launch_bounds__(1024) void k_inverse_rt(const int* __restrict__ uco
                 }
                 // ---- interp1d slope form (TM:4062-4065) and, with ETAB, exp(-x^2/4) from the located interval -------------
                 double r[NS], ev[NS];
-                auto interp = [&](double y_lo, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
-                    // (y_lo: abscissa i - 1 of the grid, fma(i, step, y0 - step) - the grid point to an ulp)
-                    // slope = step / (x_hi - x_lo): v_rcp_f64 (2^-23) with one Newton step (2^-46); its error moves x by
-                    // 0.02 x 2^-46 = 3e-16 at most.  y_hi - y_lo is the grid step up to the rounding of the two abscissae
-                    // (1e-13 of the step, also in the last interval, whose end point np.linspace forces: 2e-15 of x)
+                auto interp = [&](double y_lo, double y_hi, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
+                    // (y_lo, y_hi: abscissae i - 1 and i as np.linspace has them, to the bit - (i - 1) * step + y0 in two roundings,
+                    // the last point forced - so that this is interp1d on the rounded grid: include/ttm.h, tests/test_table_lookup.py)
+                    // slope = (y_hi - y_lo) / (x_hi - x_lo): v_rcp_f64 (2^-23) with one Newton step (2^-46); its error moves x by
+                    // 0.02 x 2^-46 = 3e-16 at most
                     const double dx = fmax(x_hi - x_lo, 1e-300);             // (tie at a flat start: table_lookup)
                     double rc = approx_rcp(dx);
                     rc = fma(fma(-dx, rc, 1.0), rc, rc);
-                    const double slope = ystep * rc;
+                    const double slope = (y_hi - y_lo) * rc;
                     const double delta = slope * (tgt - x_lo);
                     rr = delta + y_lo;
                     if (ETAB) {
@@ -1818,10 +1817,10 @@ __global__ __launch_bounds__(1024) void k_inverse_rt(const int* __restrict__ uco
 #pragma unroll
                 for (int e = 0; e < NS; ++e) {
                     const int i = pos[e];                    // (in [w0 + 1, w0 + W - 2] for a target in [wl, wh])
-                    double e_lo = 0.0, y_lo;
-                    if (ETAB) load_pair(etabw + 2 * (i - 1), e_lo, y_lo);
-                    else y_lo = fma((double)i, ystep, y0m);
-                    interp(y_lo, xsl[i - 1], xsl[i], e_lo, tg[e], r[e], ev[e]);
+                    double e_lo = 0.0, y_lo, y_hi;
+                    if (ETAB) { load_pair(etabw + 2 * (i - 1), e_lo, y_lo); y_hi = etabw[2 * i + 1]; }
+                    else { y_lo = (double)(i - 1) * ystep + y0; y_hi = i == T - 1 ? ylast : (double)i * ystep + y0; }
+                    interp(y_lo, y_hi, xsl[i - 1], xsl[i], e_lo, tg[e], r[e], ev[e]);
                 }
                 if (outl != 0) {
                     // outliers (a handful per million rows of a standard-normal ensemble): clip as TM:4074-4076 does,
@@ -1844,7 +1843,7 @@ __global__ __launch_bounds__(1024) void k_inverse_rt(const int* __restrict__ uco
                                 if (xg[mid] < t) a = mid + 1; else b = mid;
                             }
                             const int i = min(max(a, 1), T - 1);
-                            interp(fma((double)i, ystep, y0m), xg[i - 1], xg[i], ETAB ? exp_q_fast((double)(i - 1) * ystep + y0) : 0.0, t, r[e],
+                            interp((double)(i - 1) * ystep + y0, i == T - 1 ? ylast : (double)i * ystep + y0, xg[i - 1], xg[i], ETAB ? exp_q_fast((double)(i - 1) * ystep + y0) : 0.0, t, r[e],
                                    ev[e]);
                         }
                     }
