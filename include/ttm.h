@@ -610,6 +610,29 @@ int ttm_score(const ttm_program* p, const double* coef, const double* fold, cons
 int ttm_logdensity(const ttm_program* p, const double* coef, const double* fold, const double* Xsoa, int64_t ldx, int64_t N,
                    double* logp, double* Gsoa, int64_t ldg, const double* g_scale, void* stream);
 
+/* ---- draws with their log-density: the root searches of an integrated-rectifier map, fused (no counterpart in the reference) ----
+ * X = S^-1(Z) for the components [k0, k1) exactly as ttm_inverse_bisect (newton = 0; cap as there) or ttm_inverse_newton
+ * (newton = 1) compute it on the same arguments - the same X and the same iters, bit for bit - and, per row,
+ *   logq[n] = sum_{k0 <= k < k1} [ -1/2 S_k(x)^2 + log( dS_k/dx_k(x) g_scale[k - k0] ) ]    (without the -(k1 - k0)/2 log 2 pi)
+ * at the row the search RETURNED: S_k and dS_k/dx_k = r(g_k) + delta are evaluated once more at the result (csrc/ttm_sample_logq.h),
+ * so S_k is z_k to the stopping rule's 1e-9 for a converged search and whatever the map gives at the returned point for one
+ * that stopped at 100 trial points, without a sign change (newton) or under a cap.  It is the log-density of the components
+ * k0 .. k1 - 1 given the columns in front of them (conditioning columns and components < k0, read from Xsoa): what
+ * ttm_logdensity gives for k0 = 0, k1 = D at the returned rows, from the searches' own forms of S_k.
+ *   logq    : N doubles;  g_scale : nullable, k1 - k0 doubles - 1 / sigma of the own columns for raw coordinates; none: 1
+ *   iters, cap : as ttm_inverse_bisect; cap must be NULL with newton = 1
+ * The launch is the plain call's - same kernel family (k_int_root_x, k_int_root or the generic k_inverse_bisect), grid, block
+ * and LDS - in its log-density instantiation, which ttm_last_kernel reports as k_int_root_x<newton,logq>, k_int_root<bisect,logq>,
+ * k_inverse_bisect<logq>, k_inverse_newton<logq> and so on.  Rows [0, N) of logq and of the inverted columns of Xsoa are
+ * written and nothing else; no result depends on rows [N, ld) of Zsoa or Xsoa.  Graph-capturable.
+ * TTM_E_UNSUPPORTED: the map is separable (run its inverse, then ttm_forward(k0, k1, Z = NULL, logdet, sigma, sumsq) on the
+ * result: logq = logdet - sumsq / 2); TTM_E_ARG: null coef / fold / Zsoa / Xsoa / iters / logq, N < 1, ldx < N or ldz < N, a cap
+ * together with newton = 1; TTM_E_LIMIT: as the plain calls.                                                              */
+int ttm_inverse_logdensity(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1,
+                           const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
+                           int32_t newton, int32_t* iters, const int32_t* cap,
+                           double* logq, const double* g_scale, void* stream);
+
 /* ---- K6/K7: objective + gradient reductions for optimize() -------------------------
  * integrated: TM:3300-3376 objective_function, TM:3435-3569 objective_function_jacobian
  *   out[0] = sum_n ( S^2/2 - log(r(g)+delta) ), out[1..] = sum_n d/dc of the same, [nonmon | mon]

@@ -23,10 +23,11 @@ int forward(const ttm_program* p, const DevProg& P, int k0, int k1, const double
             int64_t ldx, int64_t N, double* Zsoa, int64_t ldz, double* logdet, const double* sigma, double* sumsq, int grid,
             int chunk, int bd, size_t lds, int use_x, void* stream, const char** kernel_name);
 
-// root search of ttm_inverse_bisect (newton = 0: the reference's bisection sequence, TM:3842-3976) / ttm_inverse_newton
+// root search of ttm_inverse_bisect (newton = 0: the reference's bisection sequence, TM:3842-3976) / ttm_inverse_newton;
+// logq (nullable, N doubles; g_scale nullable, k1 - k0 doubles): the log-density instantiations of ttm_inverse_logdensity
 int root(const ttm_program* p, const DevProg& P, int k0, int k1, const double* coef, const double* fold, const double* Zsoa,
-         int64_t ldz, double* Xsoa, int64_t ldx, int64_t N, int32_t* iters, const int32_t* cap, int newton, int grid, int bd,
-         size_t lds, int use_x, void* stream, const char** kernel_name);
+         int64_t ldz, double* Xsoa, int64_t ldx, int64_t N, int32_t* iters, const int32_t* cap, int newton, double* logq,
+         const double* g_scale, int grid, int bd, size_t lds, int use_x, void* stream, const char** kernel_name);
 
 // objective + gradient partial sums of one component (the k_objective launch of ttm_objective / ttm_objective_host_marked)
 int objective(const ttm_program* p, const DevProg& P, int k, const double* coef_k, const double* fold_k, const double* Xsoa,

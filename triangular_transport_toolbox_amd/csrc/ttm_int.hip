@@ -19,6 +19,7 @@
 #include "ttm_dev.h"
 #include "ttm_dense.h"
 #include "ttm_xprog.h"
+#include "ttm_sample_logq.h"
 #include "ttm_int.h"
 
 using namespace ttm;
@@ -68,11 +69,14 @@ __global__ __launch_bounds__(256) void k_int_forward(DevProg P, int kfirst, int 
     }
 }
 
-template <int PH, int PP, int RECT, bool NEWTON>
+// LOGQ: the log-density instantiations of ttm_inverse_logdensity (csrc/ttm_sample_logq.h) - the row's sum over its components
+// of -1/2 S_k^2 + log(dS_k g_scale[k - k0]) at the roots, in a register, one store per row; logq / g_scale are not read without
+template <int PH, int PP, int RECT, bool NEWTON, bool LOGQ>
 __global__ __launch_bounds__(256) void k_int_root(DevProg P, int k0, int k1, int erf, const double* __restrict__ coef,
                                                   const double* __restrict__ fold, const double* __restrict__ Z, int64_t ldz,
                                                   double* X, int64_t ldx, int64_t N, int* __restrict__ iters,
-                                                  const int* __restrict__ cap) {
+                                                  const int* __restrict__ cap, double* __restrict__ logq,
+                                                  const double* __restrict__ g_scale) {
     double* slots;
     CacheStore<double> cst;
     const Prog g = make_prog_lds(P, cst, slots, erf != 0);
@@ -83,6 +87,7 @@ __global__ __launch_bounds__(256) void k_int_root(DevProg P, int k0, int k1, int
         const bool active = n < N;
         const XSoA xa{X, ldx, active ? n : 0};
         VarCache<XSoA, double> x(xa, cst);
+        double lq = 0.0;
         for (int k = k0; k < k1; ++k) {
             const Comp c = comp_at(P, k, 0, coef, fold);
             int it = 0;
@@ -90,7 +95,14 @@ __global__ __launch_bounds__(256) void k_int_root(DevProg P, int k0, int k1, int
                 const double off = nonmon_sum<double>(c, g, x);
                 const int capk = cap ? cap[k - k0] : -1;
                 const double zk = Z[(int64_t)(k - k0) * ldz + n];
-                const double r = dense_sample_root<PH, PP, RECT, NEWTON>(c, g, qws, x, w, off, zk, capk, it);
+                double r;
+                if (LOGQ) {
+                    double S, dS;
+                    r = dense_sample_root_logq<PH, PP, RECT, NEWTON>(c, g, qws, x, w, off, zk, capk, it, S, dS);
+                    lq += logq_term(S, dS, g_scale ? ((cdbl_p)g_scale)[k - k0] : 1.0);
+                } else {
+                    r = dense_sample_root<PH, PP, RECT, NEWTON>(c, g, qws, x, w, off, zk, capk, it);
+                }
                 X[(int64_t)c.kc * ldx + n] = r;
                 x.put(c.kc, r);
             }
@@ -99,6 +111,7 @@ __global__ __launch_bounds__(256) void k_int_root(DevProg P, int k0, int k1, int
             for (int off = 32; off > 0; off >>= 1) it = max(it, __shfl_down(it, off, 64));
             if ((threadIdx.x & 63) == 0 && it > 0) atomicMax(&iters[k - k0], it);
         }
+        if (LOGQ && active) logq[n] = lq;
     }
 }
 
@@ -202,10 +215,11 @@ __global__ __launch_bounds__(256) void k_int_forward_x(DevProg P, int kfirst, in
     }
 }
 
-template <int PH, int PP, int RECT, bool NEWTON>
+template <int PH, int PP, int RECT, bool NEWTON, bool LOGQ>
 __global__ __launch_bounds__(256) void k_int_root_x(DevProg P, int k0, int k1, const double* __restrict__ fold, const double* __restrict__ Z,
                                                     int64_t ldz, double* X, int64_t ldx, int64_t N, int* __restrict__ iters,
-                                                    const int* __restrict__ cap) {
+                                                    const int* __restrict__ cap, double* __restrict__ logq,
+                                                    const double* __restrict__ g_scale) {
     LdsSlots row{g_smem + threadIdx.x, (int)blockDim.x};
     Prog g;
     g.qx = (cdbl_p)P.qx; g.qw = (cdbl_p)P.qw; g.erf_tab = nullptr; g.Q = P.Q; g.family = P.family; g.mono = P.mono; g.rect = P.rect;
@@ -218,6 +232,7 @@ __global__ __launch_bounds__(256) void k_int_root_x(DevProg P, int k0, int k1, c
         const bool active = n < N;
         // (columns of the components solved so far are read back from X: this lane wrote them itself)
         const XSoA xa{X, ldx, active ? n : 0};
+        double lq = 0.0;
         for (int k = k0; k < k1; ++k) {
             XProg xp;
             xprog_view((cint_p)P.itab + off[k], (cdbl_p)P.dpar + off[D1 + k], xp);
@@ -226,7 +241,14 @@ __global__ __launch_bounds__(256) void k_int_root_x(DevProg P, int k0, int k1, c
             if (active) {
                 const int capk = cap ? cap[k - k0] : -1;
                 const double zk = Z[(int64_t)(k - k0) * ldz + n];
-                const double r = xprog_sample_root<PH, PP, RECT, NEWTON>(xp, g, qws, fx, xa, row, zk, capk, it);
+                double r;
+                if (LOGQ) {
+                    double S, dS;
+                    r = xprog_sample_root_logq<PH, PP, RECT, NEWTON>(xp, g, qws, fx, xa, row, zk, capk, it, S, dS);
+                    lq += logq_term(S, dS, g_scale ? ((cdbl_p)g_scale)[k - k0] : 1.0);
+                } else {
+                    r = xprog_sample_root<PH, PP, RECT, NEWTON>(xp, g, qws, fx, xa, row, zk, capk, it);
+                }
                 X[(int64_t)xp.kc * ldx + n] = r;
             }
             // wave-level max, one atomic per wave (the sample-0 guard of the reference's loop needs the largest count)
@@ -234,6 +256,7 @@ __global__ __launch_bounds__(256) void k_int_root_x(DevProg P, int k0, int k1, c
             for (int o = 32; o > 0; o >>= 1) it = max(it, __shfl_down(it, o, 64));
             if ((threadIdx.x & 63) == 0 && it > 0) atomicMax(&iters[k - k0], it);
         }
+        if (LOGQ && active) logq[n] = lq;
     }
 }
 
@@ -426,36 +449,42 @@ int forward(const ttm_program* p, const DevProg& P, int k0, int k1, const double
 }
 
 int root(const ttm_program* p, const DevProg& P, int k0, int k1, const double* coef, const double* fold, const double* Zsoa,
-         int64_t ldz, double* Xsoa, int64_t ldx, int64_t N, int32_t* iters, const int32_t* cap, int newton, int grid, int bd,
-         size_t lds, int use_x, void* stream, const char** kernel_name) {
+         int64_t ldz, double* Xsoa, int64_t ldx, int64_t N, int32_t* iters, const int32_t* cap, int newton, double* logq,
+         const double* g_scale, int grid, int bd, size_t lds, int use_x, void* stream, const char** kernel_name) {
     DenseClass cls;
     if (!dense_range_class(p->h_complex, k0, k1, cls)) return TTM_E_UNSUPPORTED;
     const int erf = needs_erf(p, k0, k1);
     const int xrows = use_x ? xprog_rows(p, k0, k1) : 0;
+    // the four instantiations of a kernel for an order class and rectifier: search method x plain / with the log-density
+#define TTM_ROOT_LAUNCH(KERN, LDS, ...)                                                                                     \
+    do {                                                                                                                    \
+        if (newton && logq) hipLaunchKernelGGL((KERN<PH_, PP_, RECT_, true, true>), dim3(grid), dim3(bd), LDS, (hipStream_t)stream, __VA_ARGS__); \
+        else if (newton) hipLaunchKernelGGL((KERN<PH_, PP_, RECT_, true, false>), dim3(grid), dim3(bd), LDS, (hipStream_t)stream, __VA_ARGS__);   \
+        else if (logq) hipLaunchKernelGGL((KERN<PH_, PP_, RECT_, false, true>), dim3(grid), dim3(bd), LDS, (hipStream_t)stream, __VA_ARGS__);     \
+        else hipLaunchKernelGGL((KERN<PH_, PP_, RECT_, false, false>), dim3(grid), dim3(bd), LDS, (hipStream_t)stream, __VA_ARGS__);              \
+    } while (0)
     if (xrows > 0 && (size_t)xrows * bd * sizeof(double) <= 64 * 1024) {
         const size_t xlds = (size_t)xrows * bd * sizeof(double);
 #define TTM_CALL(PH, PP, RECT)                                                                                              \
     do {                                                                                                                    \
-        if (newton) hipLaunchKernelGGL((k_int_root_x<PH, PP, RECT, true>), dim3(grid), dim3(bd), xlds, (hipStream_t)stream, P, k0, k1, \
-                                       fold, Zsoa, ldz, Xsoa, ldx, N, (int*)iters, (const int*)cap);                        \
-        else hipLaunchKernelGGL((k_int_root_x<PH, PP, RECT, false>), dim3(grid), dim3(bd), xlds, (hipStream_t)stream, P, k0, k1,      \
-                                fold, Zsoa, ldz, Xsoa, ldx, N, (int*)iters, (const int*)cap);                               \
+        constexpr int PH_ = PH, PP_ = PP, RECT_ = RECT;                                                                     \
+        TTM_ROOT_LAUNCH(k_int_root_x, xlds, P, k0, k1, fold, Zsoa, ldz, Xsoa, ldx, N, (int*)iters, (const int*)cap, logq, g_scale); \
     } while (0)
         TTM_DENSE_DISPATCH(TTM_CALL, cls, p->rectifier);
 #undef TTM_CALL
-        *kernel_name = newton ? "k_int_root_x<newton>" : "k_int_root_x<bisect>";
+        *kernel_name = logq ? (newton ? "k_int_root_x<newton,logq>" : "k_int_root_x<bisect,logq>")
+                            : (newton ? "k_int_root_x<newton>" : "k_int_root_x<bisect>");
         return TTM_OK;
     }
 #define TTM_CALL(PH, PP, RECT)                                                                                              \
     do {                                                                                                                    \
-        if (newton) hipLaunchKernelGGL((k_int_root<PH, PP, RECT, true>), dim3(grid), dim3(bd), lds, (hipStream_t)stream, P, k0, k1, \
-                                       erf, coef, fold, Zsoa, ldz, Xsoa, ldx, N, (int*)iters, (const int*)cap);              \
-        else hipLaunchKernelGGL((k_int_root<PH, PP, RECT, false>), dim3(grid), dim3(bd), lds, (hipStream_t)stream, P, k0, k1, erf,  \
-                                coef, fold, Zsoa, ldz, Xsoa, ldx, N, (int*)iters, (const int*)cap);                          \
+        constexpr int PH_ = PH, PP_ = PP, RECT_ = RECT;                                                                     \
+        TTM_ROOT_LAUNCH(k_int_root, lds, P, k0, k1, erf, coef, fold, Zsoa, ldz, Xsoa, ldx, N, (int*)iters, (const int*)cap, logq, g_scale); \
     } while (0)
     TTM_DENSE_DISPATCH(TTM_CALL, cls, p->rectifier);
 #undef TTM_CALL
-    *kernel_name = newton ? "k_int_root<newton>" : "k_int_root<bisect>";
+#undef TTM_ROOT_LAUNCH
+    *kernel_name = logq ? (newton ? "k_int_root<newton,logq>" : "k_int_root<bisect,logq>") : (newton ? "k_int_root<newton>" : "k_int_root<bisect>");
     return TTM_OK;
 }
 

@@ -29,6 +29,7 @@
 #include "ttm_eval.h"
 #include "ttm_dev.h"
 #include "ttm_dense.h"
+#include "ttm_sample_logq.h"
 #include "ttm_rng.h"
 #include "ttm_uform.h"
 #include "ttm_score.h"
@@ -2265,12 +2266,15 @@ __global__ __launch_bounds__(256) void k_inverse_table(DevProg P, int k0, int k1
 // K5: bisection inverse
 // ---------------------------------------------------------------------------
 
-template <int MONO, bool NEWTON>
+// LOGQ (integrated maps, ttm_inverse_logdensity): also the row's log-density at the roots, logq[n] = sum_k of
+// -1/2 S_k^2 + log(dS_k g_scale[k - k0]) (csrc/ttm_sample_logq.h) - a register per row, one store; not read without
+template <int MONO, bool NEWTON, bool LOGQ = false>
 __global__ __launch_bounds__(256) void k_inverse_bisect(DevProg P, int k0, int k1, const double* __restrict__ coef,
                                                         const double* __restrict__ fold,
                                                         const double* __restrict__ Z, int64_t ldz,
                                                         double* X, int64_t ldx, int64_t N,
-                                                        int* __restrict__ iters, const int* __restrict__ cap) {
+                                                        int* __restrict__ iters, const int* __restrict__ cap,
+                                                        double* __restrict__ logq, const double* __restrict__ g_scale) {
     double* slots;
     CacheStore<double> cst;
     const Prog g = make_prog_lds(P, cst, slots);
@@ -2280,6 +2284,7 @@ __global__ __launch_bounds__(256) void k_inverse_bisect(DevProg P, int k0, int k
         const bool active = n < N;
         const XSoA xa{X, ldx, active ? n : 0};
         VarCache<XSoA, double> x(xa, cst);
+        double lq = 0.0;
         for (int k = k0; k < k1; ++k) {
             const Comp c = comp_at(P, k, 0, coef, fold);
             int it = 0;
@@ -2287,7 +2292,14 @@ __global__ __launch_bounds__(256) void k_inverse_bisect(DevProg P, int k0, int k
                 const double off = nonmon_sum<double>(c, g, x);
                 const int capk = cap ? cap[k - k0] : -1;
                 const double zk = Z[(int64_t)(k - k0) * ldz + n];
-                const double r = sample_root<MONO, NEWTON>(c, g, x, w, off, zk, capk, it);
+                double r;
+                if (LOGQ) {
+                    double S, dS;
+                    r = sample_root_logq<MONO, NEWTON>(c, g, x, w, off, zk, capk, it, S, dS);
+                    lq += logq_term(S, dS, g_scale ? ((cdbl_p)g_scale)[k - k0] : 1.0);
+                } else {
+                    r = sample_root<MONO, NEWTON>(c, g, x, w, off, zk, capk, it);
+                }
                 X[(int64_t)c.kc * ldx + n] = r;
                 x.put(c.kc, r);
             }
@@ -2296,6 +2308,7 @@ __global__ __launch_bounds__(256) void k_inverse_bisect(DevProg P, int k0, int k
             for (int off = 32; off > 0; off >>= 1) it = max(it, __shfl_down(it, off, 64));
             if ((threadIdx.x & 63) == 0 && it > 0) atomicMax(&iters[k - k0], it);
         }
+        if (LOGQ && active) logq[n] = lq;
     }
 }
 
@@ -3833,7 +3846,7 @@ int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* f
     if (!bd) return set_err(TTM_E_LIMIT, "ttm_inverse_bisect: %s%lld scratch slots do not fit the LDS budget", "", ns);
     if (tuning().int_dense != 0 && ttm_int::usable(p, k0, k1)) {
         const char* name = nullptr;
-        if (ttm_int::root(p, dev_prog(p), k0, k1, coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, cap, 0, int_grid_for(N, bd), bd, lds_bytes(ns, bd, 0),
+        if (ttm_int::root(p, dev_prog(p), k0, k1, coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, cap, 0, nullptr, nullptr, int_grid_for(N, bd), bd, lds_bytes(ns, bd, 0),
                           tuning().int_xprog == 2, stream, &name) == TTM_OK)
             return check_launch(name);
     }
@@ -3854,7 +3867,7 @@ int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* f
         if (N >= 2 && (uintptr_t)Zsoa % 16 == 8 && (uintptr_t)Xsoa % 16 == 8 && ldz % 2 == 0 && ldx % 2 == 0 && ldz >= need && ldx >= need &&
             ttm_band::bisect_plans(p, U, k0, k1, Zsoa + 1, ldz, Xsoa + 1, ldx, N - 1, iters, band_cus(), device_info().lds_per_cu, tuning().rt_block)) {
             hipLaunchKernelGGL(kern, dim3(1), dim3(bd), lds_bytes(ns, bd, 0), (hipStream_t)stream, dev_prog(p), (int)k0, (int)k1, coef, fold, Zsoa,
-                               ldz, Xsoa, ldx, (int64_t)1, iters, (const int32_t*)nullptr);
+                               ldz, Xsoa, ldx, (int64_t)1, iters, (const int32_t*)nullptr, (double*)nullptr, (const double*)nullptr);
             rc = check_launch("k_inverse_bisect");
             if (rc) return rc;
             if (ttm_band::bisect(p, U, k0, k1, Zsoa + 1, ldz, Xsoa + 1, ldx, N - 1, iters, band_cus(), device_info().lds_per_cu, tuning().rt_block,
@@ -3864,7 +3877,7 @@ int ttm_inverse_bisect(const ttm_program* p, const double* coef, const double* f
         }
     }
     hipLaunchKernelGGL(kern, dim3(grid_for(N, bd)), dim3(bd), lds_bytes(ns, bd, 0), (hipStream_t)stream, dev_prog(p), (int)k0, (int)k1,
-                       coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, cap);
+                       coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, cap, (double*)nullptr, (const double*)nullptr);
     return check_launch("k_inverse_bisect");
 }
 
@@ -3878,7 +3891,7 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
     if (!bd) return set_err(TTM_E_LIMIT, "ttm_inverse_newton: %s%lld scratch slots do not fit the LDS budget", "", ns);
     if (tuning().int_dense != 0 && ttm_int::usable(p, k0, k1)) {
         const char* name = nullptr;
-        if (ttm_int::root(p, dev_prog(p), k0, k1, coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, nullptr, 1, int_grid_for(N, bd), bd, lds_bytes(ns, bd, 0),
+        if (ttm_int::root(p, dev_prog(p), k0, k1, coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, nullptr, 1, nullptr, nullptr, int_grid_for(N, bd), bd, lds_bytes(ns, bd, 0),
                           tuning().int_xprog == 2, stream, &name) == TTM_OK)
             return check_launch(name);
     }
@@ -3891,8 +3904,34 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
     }
     auto kern = p->monotonicity == TTM_MONO_SEPARABLE ? k_inverse_bisect<TTM_MONO_SEPARABLE, true> : k_inverse_bisect<TTM_MONO_INTEGRATED, true>;
     hipLaunchKernelGGL(kern, dim3(grid_for(N, bd)), dim3(bd), lds_bytes(ns, bd, 0), (hipStream_t)stream, dev_prog(p), (int)k0, (int)k1,
-                       coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, (const int*)nullptr);
+                       coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, (const int*)nullptr, (double*)nullptr, (const double*)nullptr);
     return check_launch("k_inverse_newton");
+}
+
+// The root searches of an integrated-rectifier map with the log-density of the rows they return (include/ttm.h): the launch
+// plan of ttm_inverse_bisect / ttm_inverse_newton - block, grid, LDS, kernel family - with the LOGQ instantiation in it.
+int ttm_inverse_logdensity(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1, const double* Zsoa,
+                           int64_t ldz, double* Xsoa, int64_t ldx, int64_t N, int32_t newton, int32_t* iters, const int32_t* cap,
+                           double* logq, const double* g_scale, void* stream) {
+    int rc = validate(p, k0, k1);
+    if (rc) return rc;
+    if (!coef || !fold || !Zsoa || !Xsoa || !iters || !logq || N < 1 || ldx < N || ldz < N || (newton && cap))
+        return set_err(TTM_E_ARG, "ttm_inverse_logdensity: bad arguments (null pointers, N < 1, short leading dimensions, a cap with newton)%s");
+    if (p->monotonicity != TTM_MONO_INTEGRATED)
+        return set_err(TTM_E_UNSUPPORTED, "ttm_inverse_logdensity: integrated-rectifier maps only (separable maps: the inverse, then ttm_forward's density pass)%s");
+    const int ns = map_slots(p, k0, k1);
+    const int bd = pick_block(ns, 0);
+    if (!bd) return set_err(TTM_E_LIMIT, "ttm_inverse_logdensity: %s%lld scratch slots do not fit the LDS budget", "", ns);
+    if (tuning().int_dense != 0 && ttm_int::usable(p, k0, k1)) {
+        const char* name = nullptr;
+        if (ttm_int::root(p, dev_prog(p), k0, k1, coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, cap, newton ? 1 : 0, logq, g_scale, int_grid_for(N, bd), bd,
+                          lds_bytes(ns, bd, 0), tuning().int_xprog == 2, stream, &name) == TTM_OK)
+            return check_launch(name);
+    }
+    auto kern = newton ? k_inverse_bisect<TTM_MONO_INTEGRATED, true, true> : k_inverse_bisect<TTM_MONO_INTEGRATED, false, true>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(N, bd)), dim3(bd), lds_bytes(ns, bd, 0), (hipStream_t)stream, dev_prog(p), (int)k0, (int)k1,
+                       coef, fold, Zsoa, ldz, Xsoa, ldx, N, iters, (const int*)cap, logq, g_scale);
+    return check_launch(newton ? "k_inverse_newton<logq>" : "k_inverse_bisect<logq>");
 }
 
 // ---------------------------------------------------------------------------

@@ -186,3 +186,9 @@ extern "C" __attribute__((used, visibility("default"))) inline int ttm_score(con
 
 // (the log-density and score of integrated-rectifier maps: the other half of the score, with its own host-only entry point)
 #include "ttm_logdensity.h"
+
+#if !defined(__HIPCC__)
+// (host builds: the root searches that carry the log-density of their draws out, with the host-only entry point
+// ttm_inverse_logdensity - the host test double takes it from there, as the two above)
+#include "ttm_sample_logq.h"
+#endif

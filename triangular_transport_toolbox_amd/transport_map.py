@@ -1239,13 +1239,20 @@ class transport_map():
             _capi.check(rc)
         return Z, Xr
 
-    def inverse_device(self, Zs, N, coef=None, X=None, table=None):
+    def inverse_device(self, Zs, N, coef=None, X=None, table=None, logq=None, g_scale=None):
         """S^{-1}(z) for a column-major device matrix Zs (D x N) -> standardised X (d x N);
-        conditioning columns (if any) must already be in X."""
+        conditioning columns (if any) must already be in X.
+        logq (True, or a device buffer of N doubles): also the log-density of the returned rows given their conditioning columns,
+        without the -D/2 log 2 pi (_inverse_logq); the call then returns (X, logq).  g_scale (D, device): 1 / sigma of the own
+        columns for a density in raw coordinates; none: standardised coordinates."""
         coef = self._current(coef)
         X = self._cols(self._cm.d_cols, N, zero=True) if X is None else X
         if table is None:
             table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
+        if logq is not None and logq is not False:
+            logq = self._empty(N) if logq is True else logq
+            self._inverse_logq(coef, 0, self.D, Zs, X, N, table, logq, g_scale)
+            return X, logq
         if table:
             self._inverse_table(coef, 0, self.D, Zs, X, N)
         else:
@@ -1519,15 +1526,43 @@ class transport_map():
                 Xs[:E, :N].copy_(torch.from_numpy(np.ascontiguousarray(cols.T)))
         return Xs
 
-    def _inverse_export(self, coef, k0, k1, Zs, Xs, N, table):
+    def _inverse_export(self, coef, k0, k1, Zs, Xs, N, table, logq=None, g_scale=None):
         """The device half of inverse_map() and sample(): root searches of the components k0 .. k1 - 1 on the device matrix Zs,
-        then the layout change back (one page-locked copy) without the conditioning columns."""
-        if table:
+        then the layout change back (one page-locked copy) without the conditioning columns.  logq (a device buffer of N
+        doubles): filled with the log-density of the rows as well (_inverse_logq)."""
+        if logq is not None:
+            self._inverse_logq(coef, k0, k1, Zs, Xs, N, table, logq, g_scale)
+        elif table:
             self._inverse_table(coef, k0, k1, Zs, Xs, N)
         else:
             self._inverse_bisect(coef, k0, k1, Zs, Xs, N)
         X = self._export(Xs, N, 0, self._cm.d_cols, self.standardize_samples)
         return X[:, self.skip_dimensions:]
+
+    def _inverse_logq(self, coef, k0, k1, Zs, Xs, N, table, logq, g_scale=None):
+        """The configured inverse of the components k0 .. k1 - 1 and, into logq (N doubles on the device), the log-density of
+        the rows it returns given the columns in front of component k0, without the -(k1 - k0)/2 log 2 pi:
+            logq[n] = sum_k [ -1/2 S_k(x)^2 + log(dS_k/dx_k(x) g_scale[k - k0]) ],
+        g_scale (k1 - k0, device) = 1 / sigma of the own columns for raw coordinates, none for standardised ones.
+        Integrated-rectifier maps: one launch, the root search carries the sum out (ttm_inverse_logdensity) - the same X as the
+        plain search.  Separable maps - table, reference bisection or Newton, whichever is configured - are a composition: the
+        plain inverse, then the density pass of ttm_forward over [k0, k1) on the returned matrix (sigma = 1 / g_scale), and
+        logq = logdet - sumsq / 2.  That is the change-of-variables density of the draws with every component evaluated on
+        the standardised sample - NOT the convention of evaluate_pullback_density, which follows the reference in taking the
+        log-determinant's derivative basis on the raw sample."""
+        torch = _torch()
+        if self.monotonicity.lower() != 'separable monotonicity':
+            self._inverse_bisect(coef, k0, k1, Zs, Xs, N, logq=logq, g_scale=g_scale)
+            return
+        if table:
+            self._inverse_table(coef, k0, k1, Zs, Xs, N)
+        else:
+            self._inverse_bisect(coef, k0, k1, Zs, Xs, N)
+        logdet, sumsq = self._empty(N), self._empty(N)
+        sigma = None if g_scale is None else torch.reciprocal(g_scale)
+        _capi.check(self._lib.ttm_forward(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), self._ptr(Xs), Xs.shape[1], N, k0, k1,
+                                          None, N, self._ptr(logdet), self._ptr(sigma), self._ptr(sumsq), self._stream()))
+        logq[:N].copy_(logdet - 0.5 * sumsq)
 
     # ---- sampling: reference draws made where the inverse reads them (no counterpart in the reference: its callers draw Z with
     # scipy.stats.norm.rvs on the host, example_01.py:270-273, example_03.py:201-204) -----------------------------------------------------------------------
@@ -1570,15 +1605,16 @@ class transport_map():
                                               self._stream()))
         return Z
 
-    def sample_device(self, N, seed=0, draw=None, row0=0, X=None, Z=None, sequence='random', scramble=True):
+    def sample_device(self, N, seed=0, draw=None, row0=0, X=None, Z=None, sequence='random', scramble=True, logq=None, g_scale=None):
         """N draws from the fitted density, device-resident: reference draws (into Z, if given) pushed through the map's
         configured inverse - inverse_device(reference_device(N, seed, draw, row0=row0), N, X=X), nothing crosses PCIe.
         Conditioning columns (if any) must already be in X.  Returns the standardised (d, ld) matrix.  sequence, scramble:
-        as reference_device."""
+        as reference_device.  logq (True or a device buffer of N doubles), g_scale: as inverse_device - the call then returns
+        (X, logq), the draws with their log-density (without the -D/2 log 2 pi), device-resident."""
         Z = self.reference_device(N, seed=seed, draw=draw, row0=row0, out=Z, sequence=sequence, scramble=scramble)
-        return self.inverse_device(Z, N, X=X)
+        return self.inverse_device(Z, N, X=X, logq=logq, g_scale=g_scale)
 
-    def sample(self, N, X_star=None, seed=0, draw=None, row0=0, sequence='random', scramble=True):
+    def sample(self, N, X_star=None, seed=0, draw=None, row0=0, sequence='random', scramble=True, logdensity=False):
         """N draws from the fitted density as an N x D NumPy array: inverse_map(Z, X_star) for the reference draws
         Z = reference_device(N, seed, draw, ncols = components to invert, col0 = the first of them, row0), which never leave the
         device.  X_star: the three conditioning shapes of inverse_map - component k always takes column k of the draws, so a
@@ -1586,7 +1622,14 @@ class transport_map():
         (E,) / (1, E) for all N rows.  draw None: the map's own counter (a fresh draw per call); row0: as reference_device.
         sequence 'sobol' (scramble True): a randomised quasi-Monte Carlo sample - averages over it are unbiased estimates whose
         error falls nearly as 1 / N for smooth integrands, and calls with successive draws are the independent replicates of
-        an error bar."""
+        an error bar.
+        logdensity True: returns (X, logq), logq an (N,) array - the log-density of every draw under the fitted map in RAW
+        coordinates, log q(x) = -(D - k0)/2 log 2 pi + sum_{k >= k0} [ -1/2 S_k(u)^2 + log(dS_k/du_k / sigma_k) ] at the returned
+        row, k0 the first inverted component: with X_star the CONDITIONAL log-density log q(x_own | X_star) of the drawn block.
+        X is the same array, bit for bit, as without the keyword.  Integrated-rectifier maps get it from the root search's own
+        launch; separable maps from one density pass behind the inverse (_inverse_logq: the change-of-variables density of the
+        draws in standardised evaluation, not the raw-sample log-determinant convention of evaluate_pullback_density).  What
+        importance weights, independence Metropolis-Hastings and effective-sample-size diagnostics of the fit need."""
         N = int(N)
         if N < 1:
             raise ValueError('N must be at least 1')
@@ -1596,7 +1639,15 @@ class transport_map():
         one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
         Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
         Zs = self.reference_device(N, seed=seed, draw=draw, ncols=self.D - k0, col0=k0, row0=row0, sequence=sequence, scramble=scramble)
-        return self._inverse_export(coef, k0, self.D, Zs, Xs, N, table)
+        if not logdensity:
+            return self._inverse_export(coef, k0, self.D, Zs, Xs, N, table)
+        g_scale = None
+        if self.standardize_samples:
+            c0 = self._cm.d_cols - self.D + k0          # (column of component k0)
+            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:c0 + self.D - k0]))
+        logq = self._empty(N)
+        X = self._inverse_export(coef, k0, self.D, Zs, Xs, N, table, logq=logq, g_scale=g_scale)
+        return X, logq[:N].cpu().numpy() - 0.5 * (self.D - k0) * np.log(2 * np.pi)
 
     def _inverse_table(self, coef, k0, k1, Zs, Xs, N, resolution=1001, start_distance=10, row0=0):
         """TM:3987-4084 for all components: tabulate, index and look up on the device.  interp1d sorts its
@@ -1663,7 +1714,7 @@ class transport_map():
                                                 self._ptr(tab_y_d), resolution, resolution, None, self._ptr(tmin_d),
                                                 self._ptr(tmax_d), ctypes.c_void_p(bkt_d.data_ptr()), nb, trunc, None, 0, st))
 
-    def _inverse_bisect(self, coef, k0, k1, Zs, Xs, N, row0=0, iters=None):
+    def _inverse_bisect(self, coef, k0, k1, Zs, Xs, N, row0=0, iters=None, logq=None, g_scale=None):
         """TM:3798-3985.  Samples 1..N-1 run to convergence and record the largest
         midpoint-iteration count per component; global sample 0 is then replayed
         with that count as its cap, which is what the reference's
@@ -1674,15 +1725,33 @@ class transport_map():
         With ``root_finder = 'newton'`` (an extension, off by default): safeguarded Newton steps inside the same
         bracket and with the same stopping rule - the same roots to |S - z| <= 1e-9 in a fifth of the evaluations,
         not the reference's last midpoints and without its sample-0 quirk.  Rows are independent there: `row0` / `iters`
-        let the host pipeline send chunks of rows with one counter, which it reads after the last chunk."""
+        let the host pipeline send chunks of rows with one counter, which it reads after the last chunk.
+        logq (N doubles on the device, integrated-rectifier maps; g_scale: k1 - k0 factors or None): every call below is
+        ttm_inverse_logdensity instead, the same search with the row's log-density carried out - row n of the call's window
+        into logq[n]; the capped replay of sample 0 writes logq[0]."""
         torch = _torch()
         ncomp = k1 - k0
+        fold = coef._ttm_fold
+
+        def bisect(first, n, its, cap):
+            args = (self._pp, self._ptr(coef), self._ptr(fold), k0, k1, self._ptr(Zs, first), Zs.shape[1], self._ptr(Xs, first), Xs.shape[1], n)
+            cap = None if cap is None else ctypes.c_void_p(cap.data_ptr())
+            if logq is None:
+                return self._lib.ttm_inverse_bisect(*args, ctypes.c_void_p(its.data_ptr()), cap, self._stream())
+            return self._lib.ttm_inverse_logdensity(*args, 0, ctypes.c_void_p(its.data_ptr()), cap, self._ptr(logq, first), self._ptr(g_scale),
+                                                    self._stream())
+
         if self.root_finder == 'newton':
             own = iters is None
             if own:
                 iters = self._zeros(ncomp, dtype=torch.int32)
-            _capi.check(self._lib.ttm_inverse_newton(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), k0, k1, self._ptr(Zs, row0), Zs.shape[1],
-                                                     self._ptr(Xs, row0), Xs.shape[1], N, ctypes.c_void_p(iters.data_ptr()), self._stream()))
+            if logq is None:
+                _capi.check(self._lib.ttm_inverse_newton(self._pp, self._ptr(coef), self._ptr(fold), k0, k1, self._ptr(Zs, row0), Zs.shape[1],
+                                                         self._ptr(Xs, row0), Xs.shape[1], N, ctypes.c_void_p(iters.data_ptr()), self._stream()))
+            else:
+                _capi.check(self._lib.ttm_inverse_logdensity(self._pp, self._ptr(coef), self._ptr(fold), k0, k1, self._ptr(Zs, row0), Zs.shape[1],
+                                                             self._ptr(Xs, row0), Xs.shape[1], N, 1, ctypes.c_void_p(iters.data_ptr()), None,
+                                                             self._ptr(logq, row0), self._ptr(g_scale), self._stream()))
             if own and self.verbose and int(iters.max().item()) >= 100:
                 print('WARNING: root search stopped at maximum iterations.')
             return
@@ -1691,15 +1760,11 @@ class transport_map():
         owns_first = dist is None or dist.get_rank() == 0
         first = 1 if owns_first else 0
         if N - first > 0:
-            _capi.check(self._lib.ttm_inverse_bisect(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), k0, k1, self._ptr(Zs, first), Zs.shape[1],
-                                                     self._ptr(Xs, first), Xs.shape[1], N - first,
-                                                     ctypes.c_void_p(iters.data_ptr()), None, self._stream()))
+            _capi.check(bisect(first, N - first, iters, None))
         self._allreduce(iters, op='max')
         if owns_first:
             dummy = self._zeros(ncomp, dtype=torch.int32)
-            _capi.check(self._lib.ttm_inverse_bisect(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), k0, k1, self._ptr(Zs), Zs.shape[1], self._ptr(Xs), Xs.shape[1], 1,
-                                                     ctypes.c_void_p(dummy.data_ptr()), ctypes.c_void_p(iters.data_ptr()),
-                                                     self._stream()))
+            _capi.check(bisect(0, 1, dummy, iters))
         if self.verbose and int(iters.max().item()) >= 100:
             print('WARNING: root search stopped at maximum iterations.')
 
