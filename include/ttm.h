@@ -771,6 +771,60 @@ int ttm_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, int32_t
 int ttm_sobol_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, const uint32_t* dirs, const uint32_t* shift,
                           int64_t row0, void* stream);
 
+/* ---- importance weights in fixed point, and resampling (no counterpart in the reference) -----------------------------
+ * From N log-weights logw (device; typically log p - log q of the draws of a fitted map) to an equally weighted ensemble of M
+ * rows, with all resampling arithmetic on unsigned 64-bit integers: the scan is associative, so cum - and with it every
+ * ancestor - is a function of the log-weights alone, not of the tile, the launch or a later sharding of the rows
+ * (csrc/ttm_resample.h).  For 1 <= N <= 2^30:
+ *   m     = the maximum of the entries that are neither NaN nor +inf (-inf if there is none)
+ *   K     = min(40, 62 - ceil(log2 N))                                                (40 up to N = 2^22)
+ *   q_i   = min(2^K, floor(exp(logw_i - m) 2^K));  exactly 2^K in the row(s) of the maximum;  0 for -inf, NaN and +inf - the
+ *           last two are counted as `bad`.  exp is fast_exp of csrc/ttm_math.h (<= 1 ulp): q_i is within 1 of the exact floor.
+ *   cum_i = q_0 + ... + q_i,   T = cum_{N-1} <= 2^62
+ * A weight below 2^-K of the largest becomes 0; the mass lost is at most N 2^-K of T (9.1e-7 at N = 10^6).
+ * ttm_weight_scan writes cum (N words), q (N words, if not NULL) and the summary (device):
+ *   S2 = sum_i (q_i / 2^K)^2, non-negative doubles added in a fixed binary tree of depth at most
+ *        18 + ceil(ceil(N / 1024) / 256)   (10 levels inside a tile of 1024 rows, one addition per pass of 256 tiles, 8 levels
+ *        over the 256 running sums), so its relative error is below (depth + 2) 2^-53; the effective sample size is
+ *        (T / 2^K)^2 / S2 and the mean weight exp(m) T / (2^K N).
+ * work: caller-owned, device, TTM_WEIGHT_SCAN_WORK_WORDS(N) words of 8 bytes; it need not be initialised and what it held does
+ * not change any result.  logw, cum, q, summary and work must not overlap.  Five launches (block maxima, their finish, tile
+ * sums, scan of the tile sums, cum), no workgroup waits for another one, no atomics, no host synchronisation, graph-capturable.
+ * Rows [0, N) of cum / q are written and nothing else; no alignment beyond 8 bytes (16-byte accesses where the address allows).
+ * TTM_E_ARG: null logw, cum, summary or work; N < 1 or N > 2^30.
+ *
+ * ttm_resample draws M ancestors (1 <= M <= 2^30) from cum and copies their rows of a column-major matrix:
+ *   idx_j = min { i : cum_i > t_j },   Ysoa[c * ldy + j] = Xsoa[c * ldx + idx_j]   for c < ncols, j < M
+ * so a row with q_i = 0 is never chosen.  T is read from cum[N - 1] on the device.  With T = a M + b (b = T mod M), a 64-bit
+ * word R and V = mulhi64(R, T) in [0, T):
+ *   TTM_RESAMPLE_SYSTEMATIC   t_j = j a + floor((j b + V) / M) = floor((j T + V) / M), one R: that of block 0
+ *   TTM_RESAMPLE_STRATIFIED   the same with the word R_j of block j
+ *   TTM_RESAMPLE_MULTINOMIAL  t_j = mulhi64(R_j, T)
+ *   R_j = r[0] << 32 | r[1] of philox4x32_10(counter {lo32(j), hi32(j), 0xFFFFFFFF - scheme, 0x80000000 | draw},
+ *                                            key {lo32(seed), hi32(seed)})
+ * - blocks disjoint from ttm_normal_fill's (third word a column number < 2^31) and ttm_perturb's (fourth word 0x5EED), so a
+ * resampling is independent of the reference draws of the same (seed, draw).  An ancestor is a function of (cum, M, scheme,
+ * seed, draw, j) alone.  T = 0 (no valid weight): every idx_j is -1 and every copied entry NaN.
+ * idx (M int32, may be NULL): the ancestors; ncols = 0 with idx: the ancestors alone (Xsoa / Ysoa are not read).
+ * Rows [0, M) of the ncols columns of Ysoa and idx[0, M) are written and nothing else.  One launch of k_resample (one thread
+ * per offspring), no host synchronisation, graph-capturable.
+ * TTM_E_ARG: null cum; N or M outside [1, 2^30]; unknown scheme; draw >= 2^31; ncols < 0; ncols = 0 without idx; ncols > 0 with
+ * null Xsoa or Ysoa, ldx < N or ldy < M, or Xsoa and Ysoa overlapping.                                                    */
+#define TTM_RESAMPLE_SYSTEMATIC 0
+#define TTM_RESAMPLE_STRATIFIED 1
+#define TTM_RESAMPLE_MULTINOMIAL 2
+#define TTM_WEIGHT_SCAN_WORK_WORDS(N) (4 * (((N) + 1023) / 1024))
+typedef struct ttm_weight_summary {
+    double m;                    /* the maximum */
+    uint64_t T;                  /* cum[N - 1] */
+    double S2;                   /* sum (q_i / 2^K)^2 */
+    uint64_t bad;                /* NaN and +inf entries */
+} ttm_weight_summary;
+int ttm_weight_scan(const double* logw, int64_t N, uint64_t* cum, uint64_t* q, ttm_weight_summary* summary, void* work,
+                    void* stream);
+int ttm_resample(const uint64_t* cum, int64_t N, int64_t M, int32_t scheme, uint64_t seed, uint32_t draw, const double* Xsoa,
+                 int64_t ldx, int32_t ncols, double* Ysoa, int64_t ldy, int32_t* idx, void* stream);
+
 /* ---- optimisers -----------------------------------------------------------------------------------------
  * TM:3108-3114 (scipy.optimize.minimize, method 'L-BFGS-B': maxcor 10, ftol 2.22e-9, gtol 1e-5, maxls 20) as a host
  * C++ loop (csrc/ttm_lbfgsb.h: L-BFGS-B 3.0 restated, dense for the few dozen variables of a map component).

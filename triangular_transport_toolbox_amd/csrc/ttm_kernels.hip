@@ -2954,6 +2954,262 @@ static_assert(SOBOL_TILE * SOBOL_LOW <= 128 && SOBOL_TILE * SOBOL_ROWS <= 128 &&
               "k_sobol_normal_fill stages its tables with the two halves of a 256-thread workgroup");
 
 // ---------------------------------------------------------------------------
+// importance weights in fixed point and resampling (ttm_weight_scan, ttm_resample; per-row routines: csrc/ttm_resample.h)
+// ---------------------------------------------------------------------------
+// The scan kernels work on tiles of RS_TILE = 1024 rows, one workgroup of 256 threads each: thread t owns the row pairs
+// base + 2t and base + 512 + 2t, so a wave reads or writes 1 KiB at a stretch with one 16-byte access per lane where the pair is
+// 16-byte aligned and whole (otherwise one or two guarded 8-byte accesses).  Rows behind N read as -inf / 0 and are not written.
+// No kernel waits for another workgroup: reduce, scan of the tile sums, apply are separate launches.
+
+typedef unsigned long long rs_u64x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void rs_load2(const double* p, int64_t N, int64_t r, double& a, double& b) {
+    if (r + 1 < N && ((uintptr_t)(p + r) & 15) == 0) {
+        load_pair(p + r, a, b);
+    } else {
+        a = r < N ? p[r] : -INFINITY;
+        b = r + 1 < N ? p[r + 1] : -INFINITY;
+    }
+}
+
+__device__ __forceinline__ void rs_load2(const uint64_t* p, int64_t N, int64_t r, uint64_t& a, uint64_t& b) {
+    if (r + 1 < N && ((uintptr_t)(p + r) & 15) == 0) {
+        const rs_u64x2 v = *(const rs_u64x2*)(p + r);
+        a = v.x; b = v.y;
+    } else {
+        a = r < N ? p[r] : 0;
+        b = r + 1 < N ? p[r + 1] : 0;
+    }
+}
+
+__device__ __forceinline__ void rs_store2(uint64_t* p, int64_t N, int64_t r, uint64_t a, uint64_t b) {
+    if (r + 1 < N && ((uintptr_t)(p + r) & 15) == 0) {
+        const rs_u64x2 v = {a, b};
+        *(rs_u64x2*)(p + r) = v;
+    } else {
+        if (r < N) p[r] = a;
+        if (r + 1 < N) p[r + 1] = b;
+    }
+}
+
+// sums over the 256 threads of a workgroup, in every thread: a butterfly over the 64 lanes (6 levels, lanes i and i ^ d add the
+// same two numbers, so the tree is fixed) and (w0 + w1) + (w2 + w3) over the four waves (2 levels); s: 4 entries of LDS
+__device__ __forceinline__ double rs_block_sum(double v, double* s) {
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = (s[0] + s[1]) + (s[2] + s[3]);
+    __syncthreads();
+    return v;
+}
+
+__device__ __forceinline__ uint64_t rs_block_sum(uint64_t v, uint64_t* s) {
+    for (int d = 32; d >= 1; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = s[0] + s[1] + s[2] + s[3];
+    __syncthreads();
+    return v;
+}
+
+// inclusive sums over the lanes of a wave
+__device__ __forceinline__ uint64_t rs_wave_scan(uint64_t v) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v, d);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+// the maximum of the valid entries and the number of bad ones, per tile
+__global__ __launch_bounds__(RS_THREADS) void k_weight_max(const double* __restrict__ logw, int64_t N, double* __restrict__ pmax, uint64_t* __restrict__ pbad) {
+    __shared__ double s_m[4];
+    __shared__ uint64_t s_b[4];
+    const int t = (int)threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * RS_TILE;
+    double x[4];
+    rs_load2(logw, N, base + 2 * t, x[0], x[1]);
+    rs_load2(logw, N, base + RS_TILE / 2 + 2 * t, x[2], x[3]);
+    double m = -INFINITY;
+    uint64_t bad = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (weight_valid(x[i])) m = x[i] > m ? x[i] : m; else ++bad;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double o = __shfl_xor(m, d);
+        m = o > m ? o : m;
+    }
+    if ((t & 63) == 0) s_m[t >> 6] = m;
+    bad = rs_block_sum(bad, s_b);                      // (its barriers cover s_m too)
+    if (t == 0) {
+        for (int w = 0; w < 4; ++w) m = s_m[w] > m ? s_m[w] : m;
+        pmax[blockIdx.x] = m;
+        pbad[blockIdx.x] = bad;
+    }
+}
+
+// one workgroup: the maximum and the bad count of the whole column from the tiles'
+__global__ __launch_bounds__(RS_THREADS) void k_weight_max_finish(const double* __restrict__ pmax, const uint64_t* __restrict__ pbad, int64_t ntiles,
+                                                                  ttm_weight_summary* __restrict__ summary) {
+    __shared__ double s_m[4];
+    __shared__ uint64_t s_b[4];
+    const int t = (int)threadIdx.x;
+    double m = -INFINITY;
+    uint64_t bad = 0;
+    for (int64_t i = t; i < ntiles; i += RS_THREADS) {
+        const double o = pmax[i];
+        m = o > m ? o : m;
+        bad += pbad[i];
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double o = __shfl_xor(m, d);
+        m = o > m ? o : m;
+    }
+    if ((t & 63) == 0) s_m[t >> 6] = m;
+    bad = rs_block_sum(bad, s_b);
+    if (t == 0) {
+        for (int w = 0; w < 4; ++w) m = s_m[w] > m ? s_m[w] : m;
+        summary->m = m;
+        summary->bad = bad;
+    }
+}
+
+// phase A: q of the rows of a tile, their sum and the tile's part of S2; STORE: q parked in cum for phase C to reread
+template <bool STORE>
+__global__ __launch_bounds__(RS_THREADS) void k_weight_sums(const double* __restrict__ logw, int64_t N, const ttm_weight_summary* __restrict__ summary, int K,
+                                                            uint64_t* __restrict__ tsum, double* __restrict__ ts2, uint64_t* __restrict__ cum) {
+    __shared__ uint64_t s_u[4];
+    __shared__ double s_d[4];
+    const int t = (int)threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * RS_TILE + 2 * t, r1 = r0 + RS_TILE / 2;
+    const double m = summary->m;
+    double x[4];
+    rs_load2(logw, N, r0, x[0], x[1]);
+    rs_load2(logw, N, r1, x[2], x[3]);
+    uint64_t q[4];
+    for (int i = 0; i < 4; ++i) q[i] = weight_q(x[i], m, K);
+    if (STORE) {
+        rs_store2(cum, N, r0, q[0], q[1]);
+        rs_store2(cum, N, r1, q[2], q[3]);
+    }
+    const uint64_t sum = rs_block_sum(q[0] + q[1] + q[2] + q[3], s_u);
+    const double s2 = rs_block_sum((weight_sq(q[0], K) + weight_sq(q[1], K)) + (weight_sq(q[2], K) + weight_sq(q[3], K)), s_d);
+    if (t == 0) {
+        tsum[blockIdx.x] = sum;
+        ts2[blockIdx.x] = s2;
+    }
+}
+
+// phase B, one workgroup: the tile sums become the tiles' offsets (exclusive sums), RS_PASS tiles per pass with the total of the
+// passes before carried along; T and S2 (every thread adds one tile's part per pass, then the 256 running sums are added) go to the summary
+__global__ __launch_bounds__(RS_THREADS) void k_weight_tiles(uint64_t* __restrict__ tsum, const double* __restrict__ ts2, int64_t ntiles,
+                                                             ttm_weight_summary* __restrict__ summary) {
+    __shared__ uint64_t s_w[4];
+    __shared__ double s_d[4];
+    const int t = (int)threadIdx.x, wave = t >> 6;
+    uint64_t carry = 0;
+    double acc = 0.0;
+    for (int64_t p0 = 0; p0 < ntiles; p0 += RS_PASS) {
+        const int64_t i = p0 + t;
+        const uint64_t v = i < ntiles ? tsum[i] : 0;
+        if (i < ntiles) acc += ts2[i];
+        const uint64_t incl = rs_wave_scan(v);
+        if ((t & 63) == 63) s_w[wave] = incl;
+        __syncthreads();
+        uint64_t before = 0, total = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += s_w[w];
+            total += s_w[w];
+        }
+        if (i < ntiles) tsum[i] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();
+    }
+    const double s2 = rs_block_sum(acc, s_d);
+    if (t == 0) {
+        summary->T = carry;
+        summary->S2 = s2;
+    }
+}
+static_assert(RS_PASS == RS_THREADS && RS_TILE == 4 * RS_THREADS, "one tile sum per thread and pass, four rows per thread and tile");
+
+// phase C: cum of the rows of a tile from the tile's offset; REREAD: q as phase A parked it in cum, else computed again from logw
+// (the same routine on the same operands: the same q).  qout (nullable): q of the rows.
+template <bool REREAD>
+__global__ __launch_bounds__(RS_THREADS) void k_weight_apply(const double* __restrict__ logw, int64_t N, const ttm_weight_summary* __restrict__ summary, int K,
+                                                             const uint64_t* __restrict__ tsum, uint64_t* cum, uint64_t* __restrict__ qout) {
+    __shared__ uint64_t s_a[4], s_b[4];
+    const int t = (int)threadIdx.x, wave = t >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * RS_TILE + 2 * t, r1 = r0 + RS_TILE / 2;
+    uint64_t q[4];
+    if (REREAD) {
+        rs_load2(cum, N, r0, q[0], q[1]);
+        rs_load2(cum, N, r1, q[2], q[3]);
+    } else {
+        const double m = summary->m;
+        double x[4];
+        rs_load2(logw, N, r0, x[0], x[1]);
+        rs_load2(logw, N, r1, x[2], x[3]);
+        for (int i = 0; i < 4; ++i) q[i] = weight_q(x[i], m, K);
+    }
+    const uint64_t h0 = q[0] + q[1], h1 = q[2] + q[3];
+    const uint64_t i0 = rs_wave_scan(h0), i1 = rs_wave_scan(h1);
+    if ((t & 63) == 63) {
+        s_a[wave] = i0;
+        s_b[wave] = i1;
+    }
+    __syncthreads();
+    uint64_t off0 = tsum[blockIdx.x], off1 = off0;     // the first row of the second half comes after all of the first
+    for (int w = 0; w < 4; ++w) {
+        off1 += s_a[w];
+        if (w < wave) {
+            off0 += s_a[w];
+            off1 += s_b[w];
+        }
+    }
+    const uint64_t c0 = off0 + (i0 - h0) + q[0], c2 = off1 + (i1 - h1) + q[2];
+    rs_store2(cum, N, r0, c0, c0 + q[1]);
+    rs_store2(cum, N, r1, c2, c2 + q[3]);
+    if (qout) {
+        rs_store2(qout, N, r0, q[0], q[1]);
+        rs_store2(qout, N, r1, q[2], q[3]);
+    }
+}
+
+// Search and gather in one kernel (ttm_resample): thread j of the grid is offspring j.  The thresholds of the systematic and the
+// stratified scheme do not decrease with j, so the first and the last offspring of a workgroup search all of cum and the others
+// only between those two ancestors - about as many rows as the workgroup has offspring when M is about N, 8 dependent loads
+// instead of 20 at N = 10^6, and neighbouring lanes then copy neighbouring or equal rows.  The multinomial thresholds have no
+// order: every thread searches all of cum (the first levels of every search are the same few lines, L2 serves them) and the
+// gather is scattered.  The word of block 0 of the systematic scheme is computed once per workgroup.
+__global__ __launch_bounds__(256) void k_resample(const uint64_t* __restrict__ cum, int64_t N, int64_t M, int scheme, uint64_t seed, uint32_t draw,
+                                                  const double* __restrict__ Xsoa, int64_t ldx, int ncols, double* __restrict__ Ysoa, int64_t ldy,
+                                                  int32_t* __restrict__ idx) {
+    __shared__ uint64_t s_R;
+    __shared__ int64_t s_lo, s_hi;
+    const int t = (int)threadIdx.x;
+    const int64_t j0 = (int64_t)blockIdx.x * 256, j = j0 + t;
+    const int64_t jlast = M - 1 < j0 + 255 ? M - 1 : j0 + 255;
+    const uint64_t T = cum[N - 1];
+    if (scheme == TTM_RESAMPLE_SYSTEMATIC) {
+        if (t == 0) s_R = resample_word(seed, draw, scheme, 0);
+        __syncthreads();
+    }
+    uint64_t thr = 0;
+    if (j <= jlast) thr = resample_threshold(T, (uint64_t)M, scheme, (uint64_t)j, scheme == TTM_RESAMPLE_SYSTEMATIC ? s_R : resample_word(seed, draw, scheme, (uint64_t)j));
+    int64_t lo = 0, hi = N;
+    if (scheme != TTM_RESAMPLE_MULTINOMIAL) {
+        if (j == j0) s_lo = cum_upper_bound(cum, 0, N, thr);
+        if (j == jlast) s_hi = cum_upper_bound(cum, 0, N, thr);
+        __syncthreads();
+        lo = s_lo;
+        hi = s_hi;                                     // (cum[hi] > thr of the last offspring >= thr, or hi = N: the search may end at hi)
+    }
+    if (j <= jlast) resample_offspring(cum, N, lo, hi, thr, j, Xsoa, ldx, ncols, Ysoa, ldy, idx);
+}
+
+// ---------------------------------------------------------------------------
 // host side: launch planning
 // ---------------------------------------------------------------------------
 
@@ -4401,6 +4657,36 @@ int ttm_sobol_normal_fill(double* Zsoa, int64_t ldz, int64_t N, int32_t ncols, c
     hipLaunchKernelGGL(k_sobol_normal_fill, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, Zsoa, ldz, N, (int)ncols, (int)tile,
                        dirs, shift, row0);
     return check_launch("k_sobol_normal_fill");
+}
+
+int ttm_weight_scan(const double* logw, int64_t N, uint64_t* cum, uint64_t* q, ttm_weight_summary* summary, void* work, void* stream) {
+    if (!weight_scan_args_ok(logw, N, cum, summary, work)) return set_err(TTM_E_ARG, "ttm_weight_scan: bad arguments%s");
+    const int64_t ntiles = (N + RS_TILE - 1) / RS_TILE;                      // <= 2^20
+    // the workspace: TTM_WEIGHT_SCAN_WORK_WORDS(N) = 4 ntiles words - tile maxima, bad counts, tile sums / offsets, parts of S2;
+    // every word that is read was written by an earlier launch of this call
+    double* pmax = (double*)work;
+    uint64_t* pbad = (uint64_t*)work + ntiles;
+    uint64_t* tsum = (uint64_t*)work + 2 * ntiles;
+    double* ts2 = (double*)work + 3 * ntiles;
+    const int K = weight_bits(N);
+    const bool reread = tuning().wscan_reread == 1;                          // (default: phase C computes q again, OPTLOG)
+    const dim3 grid((unsigned)ntiles), block(RS_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_weight_max, grid, block, 0, s, logw, N, pmax, pbad);
+    hipLaunchKernelGGL(k_weight_max_finish, dim3(1), block, 0, s, (const double*)pmax, (const uint64_t*)pbad, ntiles, summary);
+    hipLaunchKernelGGL(reread ? k_weight_sums<true> : k_weight_sums<false>, grid, block, 0, s, logw, N, (const ttm_weight_summary*)summary, K, tsum, ts2, cum);
+    hipLaunchKernelGGL(k_weight_tiles, dim3(1), block, 0, s, tsum, (const double*)ts2, ntiles, summary);
+    hipLaunchKernelGGL(reread ? k_weight_apply<true> : k_weight_apply<false>, grid, block, 0, s, logw, N, (const ttm_weight_summary*)summary, K,
+                       (const uint64_t*)tsum, cum, q);
+    return check_launch(reread ? "k_weight_apply<reread>" : "k_weight_apply");
+}
+
+int ttm_resample(const uint64_t* cum, int64_t N, int64_t M, int32_t scheme, uint64_t seed, uint32_t draw, const double* Xsoa, int64_t ldx, int32_t ncols,
+                 double* Ysoa, int64_t ldy, int32_t* idx, void* stream) {
+    if (!resample_args_ok(cum, N, M, scheme, draw, Xsoa, ldx, ncols, Ysoa, ldy, idx)) return set_err(TTM_E_ARG, "ttm_resample: bad arguments%s");
+    hipLaunchKernelGGL(k_resample, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cum, N, M, (int)scheme, seed, draw, Xsoa, ldx, (int)ncols,
+                       Ysoa, ldy, idx);
+    return check_launch("k_resample");
 }
 
 int ttm_map_columns(const double* in, int64_t ldi, const int32_t* src, const double* scale, const double* shift, int32_t ncols,

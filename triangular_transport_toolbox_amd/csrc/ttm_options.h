@@ -41,6 +41,7 @@
     X(sep_sentinel, -1)  /* 0: the evaluations of ttm_optimize_separable with ticket and completion mark whatever the grid;       \
                             2: tests - the finishing workgroup gives up at once (the failure pattern reaches the host)            */ \
     X(sep_server, -1)    /* 0: the loops of ttm_optimize_separable launch per evaluation instead of ONE evaluation server per loop      */ \
+    X(wscan_reread, -1)  /* 1: the last launch of ttm_weight_scan rereads the q its tile-sum launch parked in cum instead of forming exp again */ \
     X(roundtrip_fused, -1) /* 0: ttm_roundtrip declines (the caller makes the forward and the inverse call); 1: the fused kernel for \
                               every shape it can run, also those it is slower for (reach of three columns, density terms)          */
 

@@ -253,3 +253,6 @@ extern "C" __attribute__((used, visibility("default"))) inline int ttm_sobol_nor
     return TTM_OK;
 }
 #endif
+
+// importance weights and resampling: the Philox blocks of the thresholds and the routines of ttm_weight_scan / ttm_resample
+#include "ttm_resample.h"

@@ -37,7 +37,7 @@ import os
 
 import numpy as np
 
-from . import _capi, comm, lbfgsb, qmc, quantile, termtable
+from . import _capi, comm, lbfgsb, qmc, quantile, termtable, weights
 
 __all__ = ['transport_map']
 
@@ -1648,6 +1648,148 @@ class transport_map():
         logq = self._empty(N)
         X = self._inverse_export(coef, k0, self.D, Zs, Xs, N, table, logq=logq, g_scale=g_scale)
         return X, logq[:N].cpu().numpy() - 0.5 * (self.D - k0) * np.log(2 * np.pi)
+
+    # ---- importance weights and resampling (no counterpart in the reference): logw = log p - log q of the draws becomes weights
+    # in fixed point on the device (ttm_weight_scan), diagnostics of the fit as a proposal, and an equally weighted ensemble
+    # (ttm_resample) - include/ttm.h, DESIGN.md section 4 ----------------------------------------------------------------------
+
+    def weights_device(self, logw, N, q=False):
+        """The fixed-point weights of the N log-weights `logw` (a device tensor of doubles): a weights.Weights with cum, the
+        summary words and K, all on the device - nothing is read back here.  q True: the weights themselves are kept as well."""
+        torch = _torch()
+        N = int(N)
+        if not 1 <= N <= weights.MAX_ROWS:
+            raise ValueError('N must be in [1, 2^30]')
+        if logw.dtype != torch.float64 or logw.dim() != 1 or logw.numel() < N or not logw.is_contiguous():
+            raise ValueError('logw must be a contiguous vector of at least N doubles')
+        cum = self._empty(N, dtype=torch.int64)
+        qbuf = self._empty(N, dtype=torch.int64) if q else None
+        words = self._empty(4)
+        work = self._empty(weights.work_words(N))
+        _capi.check(self._lib.ttm_weight_scan(self._ptr(logw), N, self._ptr(cum), self._ptr(qbuf), self._ptr(words), self._ptr(work), self._stream()))
+        return weights.Weights(cum, words, N, weights.weight_bits(N), qbuf)
+
+    def _logw_device(self, logw):
+        """A vector of log-weights (NumPy or device tensor) as a contiguous device tensor of doubles."""
+        torch = _torch()
+        if isinstance(logw, torch.Tensor):
+            t = logw.to(device=self._dev, dtype=torch.float64).contiguous()
+        else:
+            t = self._to_dev(np.ascontiguousarray(logw, dtype=np.float64))
+        if t.dim() != 1 or t.numel() < 1:
+            raise ValueError('logw must be a vector of at least one log-weight')
+        return t
+
+    def importance_summary(self, logw):
+        """Diagnostics of N log-weights (NumPy array or device tensor), e.g. logw = log p(x) - log q(x) of the draws of
+        sample(..., logdensity=True): {'ess': effective sample size (sum w)^2 / sum w^2, 'log_mean_weight': log of the mean
+        weight - the evidence estimate when p is unnormalised, 'max': the largest log-weight, 'n_bad': 0}, from one pass on the
+        device (weights below 2^-K of the largest count as 0, weights.lost_mass_bound).  ValueError when entries are NaN or
+        +inf, or when no entry is finite."""
+        t = self._logw_device(logw)
+        return self.weights_device(t, t.numel()).importance_summary()
+
+    def resample_device(self, Xcols, N, logw, M=None, scheme='systematic', seed=0, draw=None, idx=False, check=True):
+        """M rows (default N) drawn from the N rows of the column-major device matrix Xcols (ncols, >= N) with probabilities
+        proportional to exp(logw) - sampling-importance-resampling, device-resident: a new (ncols, ld) matrix whose row j is
+        bit for bit the row idx_j of Xcols.  logw: a device tensor of N doubles or the weights.Weights of weights_device.
+        scheme 'systematic' (one random number, offspring counts within 1 of M w_i / sum w), 'stratified' or 'multinomial'; the
+        ancestors are a function of (the weights, M, scheme, seed, draw) alone, from Philox blocks of their own.  draw None:
+        the map's own counter.  idx True: returns (matrix, ancestors as an int32 device tensor).  check: read the summary back
+        (one small copy) and raise ValueError for NaN / +inf entries or when no weight is positive."""
+        torch = _torch()
+        N = int(N)
+        M = N if M is None else int(M)
+        sid = weights.scheme_id(scheme)
+        if not 1 <= N <= weights.MAX_ROWS or not 1 <= M <= weights.MAX_ROWS:
+            raise ValueError('N and M must be in [1, 2^30]')
+        if Xcols.dim() != 2 or Xcols.shape[1] < N or Xcols.dtype != torch.float64 or not Xcols.is_contiguous():
+            raise ValueError('Xcols must be a contiguous (ncols, >= N) matrix of doubles')
+        w = logw if isinstance(logw, weights.Weights) else self.weights_device(logw, N)
+        if w.N != N:
+            raise ValueError('the weights are those of %d rows, not %d' % (w.N, N))
+        draw = self._take_draw(draw)
+        ncols = int(Xcols.shape[0])
+        Y = self._cols(ncols, M)
+        anc = self._empty(M, dtype=torch.int32) if (idx or ncols == 0) else None
+        _capi.check(self._lib.ttm_resample(self._ptr(w.cum), N, M, sid, int(seed) % 2 ** 64, draw, self._ptr(Xcols), Xcols.shape[1], ncols,
+                                           self._ptr(Y), Y.shape[1], self._ptr(anc), self._stream()))
+        if check:
+            w.importance_summary()
+        return (Y, anc) if idx else Y
+
+    def resample(self, X, logw, M=None, scheme='systematic', seed=0, draw=None):
+        """resample_device for an N x d NumPy array: returns (M x d array, ancestors), row j of the result bit for bit row
+        idx[j] of X."""
+        X = np.asarray(X, dtype=float)
+        if X.ndim != 2 or X.shape[0] < 1:
+            raise ValueError('X must be an N x d array')
+        N = X.shape[0]
+        t = self._logw_device(logw)
+        if t.numel() != N:
+            raise ValueError('X has %d rows, logw %d entries' % (N, t.numel()))
+        M = N if M is None else int(M)
+        if M < 1:
+            raise ValueError('M must be at least 1')
+        Y, anc = self.resample_device(self._import(X, False), N, t, M=M, scheme=scheme, seed=seed, draw=draw, idx=True)
+        return self._export(Y, M, 0, X.shape[1], False), anc.cpu().numpy()
+
+    def sample_importance(self, N, log_target_pdf, M=None, X_star=None, seed=0, draw=None, sequence='random', scramble=True,
+                          scheme='systematic', target_on_device=False):
+        """Sampling-importance-resampling with the fitted map as the proposal: N draws with their log-density - those of
+        sample(N, X_star, seed, draw, sequence=..., logdensity=True), the same bits -, the weights logw = log_target_pdf(X) - logq,
+        and M rows (default N) resampled in proportion to them.  log_target_pdf gets the N x D raw draws as a NumPy array and
+        returns N values (the convention of evaluate_pushforward_density); it may be unnormalised.  target_on_device True: it
+        gets a (D, N) torch tensor of the raw coordinates on the device and returns a device tensor - then only the M resampled
+        rows cross PCIe.  The thresholds come from Philox blocks of their own, so the resampling is independent of the reference
+        draws of the same (seed, draw).  Returns (X_resampled (M x D), info): info['ess'] the effective sample size of the N
+        draws, info['log_mean_weight'] the log of the mean weight (the evidence estimate), info['idx'] the ancestors - row j is
+        row idx[j] of the draws -, info['logw'] the N log-weights.  ValueError when a weight is NaN or +inf or none is positive."""
+        torch = _torch()
+        N = int(N)
+        M = N if M is None else int(M)
+        if N < 1 or M < 1:
+            raise ValueError('N and M must be at least 1')
+        weights.scheme_id(scheme)
+        draw = self._take_draw(draw)
+        k0, E, Xstar_cols = self._conditioning(X_star)
+        coef = self._pack_coeffs()
+        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
+        one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
+        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
+        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=self.D - k0, col0=k0, sequence=sequence, scramble=scramble)
+        g_scale = None
+        if self.standardize_samples:
+            c0 = self._cm.d_cols - self.D + k0          # (column of component k0)
+            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:c0 + self.D - k0]))
+        logq = self._empty(N)
+        self._inverse_logq(coef, k0, self.D, Zs, Xs, N, table, logq, g_scale)
+        d, skip = self._cm.d_cols, self.skip_dimensions
+        const = 0.5 * (self.D - k0) * np.log(2 * np.pi)
+        if target_on_device:
+            raw = Xs[skip:d, :N]
+            if self.standardize_samples:                 # (what ttm_export computes: x * sd + mean, two roundings)
+                raw = raw * self._std_d[skip:d, None] + self._mean_d[skip:d, None]
+            logp = log_target_pdf(raw)
+            if not isinstance(logp, torch.Tensor) or logp.numel() != N:
+                raise ValueError('log_target_pdf must return a tensor of N values')
+            logw = (logp.reshape(N).to(torch.float64) - (logq[:N] - const)).contiguous()
+            w = self.weights_device(logw, N)
+            Y, anc = self.resample_device(Xs, N, w, M=M, scheme=scheme, seed=seed, draw=draw, idx=True)
+            Xr = self._export(Y, M, 0, d, self.standardize_samples)[:, skip:]
+            anc, logw = anc.cpu().numpy(), logw.cpu().numpy()
+        else:
+            X = self._export(Xs, N, 0, d, self.standardize_samples)[:, skip:]
+            logp = np.asarray(log_target_pdf(X), dtype=float).reshape(-1)
+            if logp.shape[0] != N:
+                raise ValueError('log_target_pdf must return N values')
+            logw = logp - (logq[:N].cpu().numpy() - const)
+            w = self.weights_device(self._to_dev(logw), N)
+            _, anc = self.resample_device(Xs[:0], N, w, M=M, scheme=scheme, seed=seed, draw=draw, idx=True)
+            anc = anc.cpu().numpy()
+            Xr = X[anc]
+        info = dict(w.importance_summary(), idx=anc, logw=logw)
+        return Xr, info
 
     def _inverse_table(self, coef, k0, k1, Zs, Xs, N, resolution=1001, start_distance=10, row0=0):
         """TM:3987-4084 for all components: tabulate, index and look up on the device.  interp1d sorts its
