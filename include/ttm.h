@@ -825,6 +825,45 @@ int ttm_weight_scan(const double* logw, int64_t N, uint64_t* cum, uint64_t* q, t
 int ttm_resample(const uint64_t* cum, int64_t N, int64_t M, int32_t scheme, uint64_t seed, uint32_t draw, const double* Xsoa,
                  int64_t ldx, int32_t ncols, double* Ysoa, int64_t ldy, int32_t* idx, void* stream);
 
+/* ---- one step of Metropolis-Hastings in the reference space of a fitted map (no counterpart in the reference) --------------
+ * N chains, one per row, each with a state z (reference space, ncols own components), its image x = S^-1(z) (standardised own
+ * columns) and its log-weight logw = log p(x) - log q(x), all column-major on the device.  The proposal z' = rho z + sqrt(1 -
+ * rho^2) xi, xi ~ N(0, I), is reversible with respect to N(0, I), so the acceptance ratio of the pulled-back target is
+ * w(x') / w(x) for every rho in (-1, 1) (rho = 0: the independence sampler with the map as its proposal; csrc/ttm_mcmc.h,
+ * DESIGN.md section 4).  One call decides a step that an earlier call proposed - the caller has inverted Zprop into Xprop and
+ * evaluated logw_prop in between - and / or proposes the next one.  Per row n < N (GLOBAL row g = row0 + n), in this order:
+ *   accept phase (logw_prop given): lp = logw_prop[n], lc = logw_cur[n], u the accept uniform of (seed, draw_accept, g);
+ *     lp NaN or +inf: a BAD proposal, rejected, n_bad[n] += 1;
+ *     otherwise accept = lp > -inf && (lc == -inf || log(u) < lp - lc);
+ *     accept: Zcur[j * ldzc + n] and Xcur[j * ldxc + n] take the bits of Zprop / Xprop for j < ncols, logw_out[n] = lp,
+ *     n_acc[n] += 1;  otherwise nothing of Zcur / Xcur at that row is stored and logw_out[n] = lc.
+ *     Without an accept phase logw_out (if not NULL) is a copy of logw_cur.
+ *   Xrec (if not NULL): Xrec[j * ldxr + n] = the own columns of row n after the decision, for every row.
+ *   propose phase (Znext given): Znext[j * ldzn + n] = fma(rho, z, s xi_j) with z the value of Zcur after the decision,
+ *     s = sqrt((1 - rho)(1 + rho)) (formed once on the host) and xi_j the deviate ttm_normal_fill writes for (seed,
+ *     draw_propose, col0 + j, g), bit for bit.  rho == 0: Zcur is not read for the proposal and Znext = xi_j itself.
+ * The accept uniforms come from Philox blocks of their own, block p for the global rows 2p and 2p + 1:
+ *   r = philox4x32_10(counter {lo32(p), hi32(p), 0xFFFFFFFB, 0x80000000 | draw}, key {lo32(seed), hi32(seed)})
+ *   u(row 2p) = ((r[0] << 32 | r[1]) >> 11) + 0.5) 2^-53,  u(row 2p + 1) likewise from r[2], r[3]
+ * - third word 0xFFFFFFFF - 4: disjoint from the reference draws (a column number < 2^31 there), from ttm_resample's blocks
+ * (0xFFFFFFFF - scheme, scheme <= 2) and from ttm_perturb's (fourth word 0x5EED).
+ * Every output entry is a function of (the inputs at that row, seed, the draws, the column, the global row) alone - not of N,
+ * of the window of rows, of ncols or of the launch: ranks that shard the rows pass their offset as row0.  Rows [0, N) of the
+ * outputs are written and nothing else; no result depends on rows >= N of any input.  No alignment beyond 8 bytes and no parity
+ * requirement on row0 or a leading dimension (16-byte accesses where a pair lies in the window at an aligned address).
+ * One launch of k_mh_step (one thread per global row pair; the columns may be spread over workgroups, each of which forms the
+ * decision for itself - which is why logw_out must not overlap logw_cur or logw_prop; an element of Zcur / Xcur is read and
+ * written by one thread only, so the state is updated in place).  No atomics, no host synchronisation, graph-capturable.
+ * n_acc, n_bad: nullable, N int32 each.
+ * TTM_E_ARG: null Zcur, Xcur or logw_cur; neither phase; an accept phase with null Zprop, Xprop or logw_out; logw_out
+ * overlapping logw_cur or logw_prop; N < 1, ncols < 1, col0 < 0, row0 < 0; any leading dimension < N (a NULL matrix's too);
+ * draw_accept or draw_propose >= 2^31; rho NaN or |rho| >= 1.                                                            */
+int ttm_mh_step(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out,
+                const double* Zprop, int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop,
+                double* Znext, int64_t ldzn, double rho, double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad,
+                int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept, uint32_t draw_propose,
+                int64_t row0, void* stream);
+
 /* ---- optimisers -----------------------------------------------------------------------------------------
  * TM:3108-3114 (scipy.optimize.minimize, method 'L-BFGS-B': maxcor 10, ftol 2.22e-9, gtol 1e-5, maxls 20) as a host
  * C++ loop (csrc/ttm_lbfgsb.h: L-BFGS-B 3.0 restated, dense for the few dozen variables of a map component).

@@ -3209,6 +3209,13 @@ __global__ __launch_bounds__(256) void k_resample(const uint64_t* __restrict__ c
     if (j <= jlast) resample_offspring(cum, N, lo, hi, thr, j, Xsoa, ldx, ncols, Ysoa, ldy, idx);
 }
 
+// One Metropolis-Hastings step in reference space (ttm_mh_step; csrc/ttm_mcmc.h): thread i owns pair number i of the window of
+// global rows, as in k_normal_fill, and walks the columns blockIdx.y, blockIdx.y + gridDim.y, ...  Every column group decides
+// the pair for itself from logw_cur / logw_prop, which no workgroup of the launch writes; group 0 writes logw_out and the counts.
+__global__ __launch_bounds__(256) void k_mh_step(const MhStep a) {
+    mh_step_pair(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int)blockIdx.y, (int)gridDim.y);
+}
+
 // ---------------------------------------------------------------------------
 // host side: launch planning
 // ---------------------------------------------------------------------------
@@ -4687,6 +4694,23 @@ int ttm_resample(const uint64_t* cum, int64_t N, int64_t M, int32_t scheme, uint
     hipLaunchKernelGGL(k_resample, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cum, N, M, (int)scheme, seed, draw, Xsoa, ldx, (int)ncols,
                        Ysoa, ldy, idx);
     return check_launch("k_resample");
+}
+
+int ttm_mh_step(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out, const double* Zprop, int64_t ldzp,
+                const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double* Xrec, int64_t ldxr,
+                int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept, uint32_t draw_propose,
+                int64_t row0, void* stream) {
+    const MhStep a = mh_step_pack(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, Xrec, ldxr, n_acc,
+                                  n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0);
+    if (!mh_step_args_ok(a)) return set_err(TTM_E_ARG, "ttm_mh_step: bad arguments%s");
+    const int64_t gx = (normal_fill_pairs(N, row0) + 255) / 256;
+    if (gx > 0x7fffffff) return set_err(TTM_E_LIMIT, "ttm_mh_step: %s%lld rows are more than one launch covers", "", (long long)N);
+    // the columns over blockIdx.y by the rule of ttm_normal_fill (32 workgroups per CU); no result depends on the split
+    int64_t gy = (32 * (int64_t)device_info().cus + gx - 1) / gx;
+    gy = gy < 1 ? 1 : (gy > ncols ? ncols : gy);
+    if (gy > 65535) gy = 65535;
+    hipLaunchKernelGGL(k_mh_step, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("k_mh_step");
 }
 
 int ttm_map_columns(const double* in, int64_t ldi, const int32_t* src, const double* scale, const double* shift, int32_t ncols,

@@ -1,0 +1,192 @@
+// ttm_mcmc.h - one step of Metropolis-Hastings in the reference space of a fitted map (ttm_mh_step of include/ttm.h; DESIGN.md
+// section 4): the per-pair routines the kernel k_mh_step of csrc/ttm_kernels.hip and the host definition of the entry point
+// share.  Included at the end of csrc/ttm_rng.h (philox4x32_10, normal_pair, load_pair / store_pair come from there).
+//
+// The chain of row n lives in reference space: z' = rho z + sqrt(1 - rho^2) xi is reversible with respect to N(0, I), the
+// pulled-back target is w(x(z)) phi(z) with w = p / q, so the acceptance ratio is w(x') / w(x) for every rho in (-1, 1) - the
+// independence sampler with the map as its proposal at rho = 0.  Between two launches the caller inverts the proposal and
+// evaluates the target; one launch decides the step that was proposed by the launch before it and proposes the next one.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+namespace ttm {
+
+// the arguments of ttm_mh_step as the kernel takes them (s = sqrt((1 - rho)(1 + rho)), formed once on the host)
+struct MhStep {
+    double* Zcur; int64_t ldzc;
+    double* Xcur; int64_t ldxc;
+    const double* logw_cur; double* logw_out;
+    const double* Zprop; int64_t ldzp;
+    const double* Xprop; int64_t ldxp;
+    const double* logw_prop;
+    double* Znext; int64_t ldzn;
+    double rho, s;
+    double* Xrec; int64_t ldxr;
+    int32_t* n_acc; int32_t* n_bad;
+    int64_t N; int32_t ncols, col0;
+    uint64_t seed; uint32_t draw_accept, draw_propose;
+    int64_t row0;
+};
+
+// The accept uniforms of global rows 2p and 2p + 1 of draw `draw` (< 2^31) under `seed`: one Philox block of their own, counter
+// {lo32(p), hi32(p), 0xFFFFFFFB, 0x80000000 | draw}, key {lo32(seed), hi32(seed)}; row 2p from r[0], r[1], row 2p + 1 from r[2],
+// r[3], formed as in normal_pair (0 < u < 1).  The third word is 0xFFFFFFFF - 4: the reference draws have a column number
+// below 2^31 there, resample_word 0xFFFFFFFF - scheme with scheme <= 2, and normal_deviate has 0x5EED as its fourth word.
+TTM_HD void mh_uniform_pair(uint64_t seed, uint32_t draw, uint64_t p, double& u0, double& u1) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)p, (uint32_t)(p >> 32), 0xFFFFFFFBu, 0x80000000u | draw, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    u0 = ((double)((((uint64_t)r[0] << 32) | r[1]) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    u1 = ((double)((((uint64_t)r[2] << 32) | r[3]) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+}
+
+enum { MH_REJECT = 0, MH_ACCEPT = 1, MH_BAD = 2 };
+
+// the decision of one row from the log-weight of its proposal lp, that of its current state lc and its uniform u: a proposal
+// whose weight is NaN or +inf is `bad` and rejected; one of weight zero (-inf) is rejected; a chain whose own weight is zero
+// takes the first admissible proposal
+TTM_HD int mh_decide(double lp, double lc, double u) {
+    if (lp != lp || lp == INFINITY) return MH_BAD;
+    return (lp > -INFINITY && (lc == -INFINITY || log(u) < lp - lc)) ? MH_ACCEPT : MH_REJECT;
+}
+
+// The rows n0 (if v0) and n0 + 1 (if v1) of a column: ONE 16-byte access when both are wanted and the address allows it,
+// guarded 8-byte ones otherwise.  A row that is not wanted is neither read nor written (a load returns 0 for it).
+TTM_HD bool mh_pair_aligned(const void* col, int64_t n0) { return (((uintptr_t)col + 8 * (uintptr_t)n0) & 15) == 0; }
+
+TTM_HD void mh_load2(const double* col, int64_t n0, bool v0, bool v1, double& a, double& b) {
+    if (v0 && v1 && mh_pair_aligned(col, n0)) {
+        load_pair(col + n0, a, b);
+    } else {
+        a = v0 ? col[n0] : 0.0;
+        b = v1 ? col[n0 + 1] : 0.0;
+    }
+}
+
+TTM_HD void mh_store2(double* col, int64_t n0, bool v0, bool v1, double a, double b) {
+    if (v0 && v1 && mh_pair_aligned(col, n0)) {
+        store_pair(col + n0, a, b);
+    } else {
+        if (v0) col[n0] = a;
+        if (v1) col[n0 + 1] = b;
+    }
+}
+
+// What one thread of k_mh_step does: pair number i of the window of global rows [row0, row0 + N), as normal_fill_pair owns it,
+// in the columns j0, j0 + jstep, ... < ncols.  Every column group forms the pair's decision for itself (one Philox block, two
+// pairs of log-weights); the group with j0 = 0 alone writes logw_out, n_acc and n_bad.  An element of Zcur / Xcur is read and
+// written by this thread only, so the state is updated in place.
+TTM_HD void mh_step_pair(const MhStep& a, int64_t i, int j0, int jstep) {
+    const uint64_t p = (uint64_t)(a.row0 >> 1) + (uint64_t)i;
+    const int64_t n0 = (int64_t)(2 * p - (uint64_t)a.row0);   // local row of global row 2p: -1 .. N - 1
+    if (n0 >= a.N) return;
+    const bool v0 = n0 >= 0, v1 = n0 + 1 < a.N;
+    const bool accept_phase = a.logw_prop != nullptr;
+    bool acc0 = false, acc1 = false;
+    if (accept_phase) {
+        double u0, u1, lp0, lp1, lc0, lc1;
+        mh_uniform_pair(a.seed, a.draw_accept, p, u0, u1);
+        mh_load2(a.logw_prop, n0, v0, v1, lp0, lp1);
+        mh_load2(a.logw_cur, n0, v0, v1, lc0, lc1);
+        const int d0 = v0 ? mh_decide(lp0, lc0, u0) : MH_REJECT, d1 = v1 ? mh_decide(lp1, lc1, u1) : MH_REJECT;
+        acc0 = d0 == MH_ACCEPT;
+        acc1 = d1 == MH_ACCEPT;
+        if (j0 == 0) {
+            mh_store2(a.logw_out, n0, v0, v1, acc0 ? lp0 : lc0, acc1 ? lp1 : lc1);
+            if (a.n_acc) {
+                if (acc0) a.n_acc[n0] += 1;
+                if (acc1) a.n_acc[n0 + 1] += 1;
+            }
+            if (a.n_bad) {
+                if (d0 == MH_BAD) a.n_bad[n0] += 1;
+                if (d1 == MH_BAD) a.n_bad[n0 + 1] += 1;
+            }
+        }
+    } else if (a.logw_out && j0 == 0) {
+        double lc0, lc1;
+        mh_load2(a.logw_cur, n0, v0, v1, lc0, lc1);
+        mh_store2(a.logw_out, n0, v0, v1, lc0, lc1);
+    }
+    const bool propose = a.Znext != nullptr;
+    const bool read_z = propose && a.rho != 0.0;               // (rho = 0: the state does not enter the proposal and is not read)
+    if (!propose && !a.Xrec && !(acc0 || acc1)) return;
+    for (int j = j0; j < a.ncols; j += jstep) {
+        // the loads take both rows of the pair whatever was decided - the lines are fetched whole anyway, and a wave then issues
+        // one 16-byte load per matrix instead of three divergent forms; only the stores into the state are per accepted row
+        double z0 = 0.0, z1 = 0.0, x0 = 0.0, x1 = 0.0;
+        if (read_z) mh_load2(a.Zcur + (int64_t)j * a.ldzc, n0, v0, v1, z0, z1);
+        if (a.Xrec) mh_load2(a.Xcur + (int64_t)j * a.ldxc, n0, v0, v1, x0, x1);
+        if (accept_phase) {
+            double zp0, zp1, xp0, xp1;
+            mh_load2(a.Zprop + (int64_t)j * a.ldzp, n0, v0, v1, zp0, zp1);
+            mh_load2(a.Xprop + (int64_t)j * a.ldxp, n0, v0, v1, xp0, xp1);
+            if (acc0 || acc1) {
+                mh_store2(a.Zcur + (int64_t)j * a.ldzc, n0, acc0, acc1, zp0, zp1);
+                mh_store2(a.Xcur + (int64_t)j * a.ldxc, n0, acc0, acc1, xp0, xp1);
+            }
+            z0 = acc0 ? zp0 : z0; z1 = acc1 ? zp1 : z1;
+            x0 = acc0 ? xp0 : x0; x1 = acc1 ? xp1 : x1;
+        }
+        if (a.Xrec) mh_store2(a.Xrec + (int64_t)j * a.ldxr, n0, v0, v1, x0, x1);
+        if (propose) {
+            double xi0, xi1;
+            normal_pair(a.seed, a.draw_propose, (uint32_t)a.col0 + (uint32_t)j, p, xi0, xi1);
+            if (read_z) {
+                xi0 = fma(a.rho, z0, a.s * xi0);
+                xi1 = fma(a.rho, z1, a.s * xi1);
+            }
+            mh_store2(a.Znext + (int64_t)j * a.ldzn, n0, v0, v1, xi0, xi1);
+        }
+    }
+}
+
+TTM_HD bool mh_ranges_overlap(const double* x, const double* y, int64_t N) {
+    const uintptr_t x0 = (uintptr_t)x, y0 = (uintptr_t)y, len = 8 * (uintptr_t)N;
+    return x0 < y0 + len && y0 < x0 + len;
+}
+
+// argument check of ttm_mh_step, shared by the library and the host definition below
+TTM_HD bool mh_step_args_ok(const MhStep& a) {
+    if (!a.Zcur || !a.Xcur || !a.logw_cur || a.N < 1 || a.ncols < 1 || a.col0 < 0 || a.row0 < 0 || a.N > INT64_MAX - a.row0) return false;
+    if (a.draw_accept >= 0x80000000u || a.draw_propose >= 0x80000000u) return false;
+    if (!a.logw_prop && !a.Znext) return false;                                 // neither phase
+    if (a.ldzc < a.N || a.ldxc < a.N || a.ldzp < a.N || a.ldxp < a.N || a.ldzn < a.N || a.ldxr < a.N) return false;   // (of matrices not in use too)
+    if (a.logw_prop && (!a.Zprop || !a.Xprop || !a.logw_out)) return false;
+    if (!(fabs(a.rho) < 1.0)) return false;                                      // (NaN fails the comparison)
+    if (a.logw_out && (mh_ranges_overlap(a.logw_out, a.logw_cur, a.N) || (a.logw_prop && mh_ranges_overlap(a.logw_out, a.logw_prop, a.N)))) return false;
+    return true;
+}
+
+TTM_HD MhStep mh_step_pack(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out, const double* Zprop,
+                           int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double* Xrec,
+                           int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
+                           uint32_t draw_propose, int64_t row0) {
+    MhStep a;
+    a.Zcur = Zcur; a.ldzc = ldzc; a.Xcur = Xcur; a.ldxc = ldxc; a.logw_cur = logw_cur; a.logw_out = logw_out;
+    a.Zprop = Zprop; a.ldzp = ldzp; a.Xprop = Xprop; a.ldxp = ldxp; a.logw_prop = logw_prop;
+    a.Znext = Znext; a.ldzn = ldzn; a.rho = rho; a.s = sqrt((1.0 - rho) * (1.0 + rho));
+    a.Xrec = Xrec; a.ldxr = ldxr; a.n_acc = n_acc; a.n_bad = n_bad;
+    a.N = N; a.ncols = ncols; a.col0 = col0; a.seed = seed; a.draw_accept = draw_accept; a.draw_propose = draw_propose; a.row0 = row0;
+    return a;
+}
+
+}  // namespace ttm
+
+#if !defined(__HIPCC__)
+// HOST BUILDS ONLY (as ttm_normal_fill in csrc/ttm_rng.h): the entry point ttm_mh_step of include/ttm.h for the host test double
+// of the C ABI - the kernel's thread body, pair after pair.
+extern "C" __attribute__((used, visibility("default"))) inline int ttm_mh_step(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur,
+                                                                               double* logw_out, const double* Zprop, int64_t ldzp, const double* Xprop,
+                                                                               int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho,
+                                                                               double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N,
+                                                                               int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
+                                                                               uint32_t draw_propose, int64_t row0, void*) {
+    const ttm::MhStep a = ttm::mh_step_pack(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, Xrec, ldxr,
+                                            n_acc, n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0);
+    if (!ttm::mh_step_args_ok(a)) return TTM_E_ARG;
+    const int64_t np = ttm::normal_fill_pairs(N, row0);
+    for (int64_t i = 0; i < np; ++i) ttm::mh_step_pair(a, i, 0, 1);
+    return TTM_OK;
+}
+#endif

@@ -256,3 +256,6 @@ extern "C" __attribute__((used, visibility("default"))) inline int ttm_sobol_nor
 
 // importance weights and resampling: the Philox blocks of the thresholds and the routines of ttm_weight_scan / ttm_resample
 #include "ttm_resample.h"
+
+// Metropolis-Hastings in the reference space of a fitted map: the accept uniforms and the routines of ttm_mh_step
+#include "ttm_mcmc.h"

@@ -1791,6 +1791,197 @@ class transport_map():
         info = dict(w.importance_summary(), idx=anc, logw=logw)
         return Xr, info
 
+    # ---- map-preconditioned Metropolis-Hastings (no counterpart in the reference): chains in the reference space of the map, where
+    # the target is close to a standard normal; the step is one launch (ttm_mh_step, k_mh_step) - include/ttm.h, DESIGN.md section 4 --
+
+    def mcmc_device(self, log_target_pdf, chains, steps, Xs=None, rho=0.0, burn=0, thin=1, seed=0, draw=None, row0=0, init=None, k0=0):
+        """`chains` independent Metropolis-Hastings chains (one per row) of `steps` steps in the reference space of the map,
+        device-resident.  With S the map of the components k0 .. D - 1 given the columns in front, q the density of the map's
+        draws and w = p / q, step t proposes
+            z' = rho z + sqrt(1 - rho^2) xi,   xi ~ N(0, I),   x' = S^-1(z')
+        and accepts with probability min(1, w(x') / w(x)): the proposal is reversible with respect to N(0, I) and the target
+        pulled back to z is w(x(z)) phi(z), so this is the Metropolis-Hastings ratio for every rho in (-1, 1).  rho = 0 is the
+        independence sampler with the map as its proposal; rho near 1 makes small moves that still accept when the fit is poor.
+        log_target_pdf gets the raw own coordinates as a (D - k0, chains) device tensor and returns `chains` values on the
+        device; it may be unnormalised.  Xs: a contiguous (d, width) device matrix, as _conditioned_cols makes it, with the
+        standardised conditioning columns in front (its own columns are scratch; any even width >= chains - every column then
+        starts 16-byte aligned, as _ld has it - and the state keeps its own leading dimension); None: no conditioning columns.
+        Draw numbers: the run uses draw0 .. draw0 + steps - draw0 makes the initial state, exactly sample_device(chains, seed,
+        draw0, row0, logq=...) and its weight; draw0 + t the innovations and the accept uniforms of step t.  draw None: the
+        map's counter, advanced by steps + 1.  init: an N x (D - k0) raw array of initial states (z = S(x) and log q from one
+        pass of ttm_forward over [k0, D)), or the `state` of an earlier run, which this run continues to the bits of one longer
+        run: it then takes draw0 = the last draw of that run (draw None), seed and row0 from the state (an argument that names
+        another seed or row0 than the state's raises ValueError; the default 0 stands for the state's) and makes no initial
+        state.
+        steps + 1 launches of ttm_mh_step: the first proposes, each later one decides step t and proposes step t + 1, the last
+        decides; between two of them the configured inverse with its log-density (_inverse_logq) and the target.  One read-back
+        (the check of the initial weights), nothing else leaves the device.
+        With the table inverse (alternate_root_finding = True, the default of separable maps) x' is interpolated, so the chain
+        targets the density up to the table's round-trip error (9e-5 at C5); root_finder = 'newton' with
+        alternate_root_finding = False, or an integrated-rectifier map, makes the step exact to the root tolerance.
+        Returns (trace, state): trace a (kept, D - k0, ld) device tensor, the STANDARDISED own columns after the steps
+        burn + thin, burn + 2 thin, ... <= steps; state a dict (Z, X, logw, n_acc, n_bad on the device; steps, draws, seed,
+        row0) that init= takes."""
+        torch = _torch()
+        N, steps, burn, thin, k0, row0 = int(chains), int(steps), int(burn), int(thin), int(k0), int(row0)
+        rho = float(rho)
+        if N < 1 or steps < 1 or thin < 1 or burn < 0:
+            raise ValueError('chains, steps and thin must be at least 1 and burn at least 0')
+        kept = (steps - burn) // thin
+        if kept < 1:
+            raise ValueError('no state is kept: burn + thin must be at most steps')
+        if not abs(rho) < 1.0:
+            raise ValueError('rho must lie in (-1, 1)')
+        if not 0 <= k0 < self.D or row0 < 0:
+            raise ValueError('k0 must be in [0, D) and row0 at least 0')
+        cont = isinstance(init, dict)
+        ncols, d = self.D - k0, self._cm.d_cols
+        c0 = d - ncols                                   # (column of component k0)
+        ld = self._ld(N)
+        seed64 = int(seed) % 2 ** 64
+        if cont:
+            for key, shape, dtype in (('Z', (ncols, ld), torch.float64), ('X', (ncols, ld), torch.float64), ('logw', (N,), torch.float64),
+                                      ('n_acc', (N,), torch.int32), ('n_bad', (N,), torch.int32)):
+                v = init.get(key)
+                if not isinstance(v, torch.Tensor) or tuple(v.shape) != shape or v.dtype != dtype or v.device.type != self._dev.type or not v.is_contiguous():
+                    raise ValueError('init is not the state of %d chains of %d components' % (N, ncols))
+            try:
+                done, last = int(init['steps']), int(init['draws'][1])
+                seed_s, row0_s = int(init['seed']), int(init['row0'])
+            except (KeyError, TypeError, ValueError, IndexError):
+                raise ValueError('init is not the state of an earlier run: steps, draws, seed or row0 is missing') from None
+            # a continuation runs on the random stream of the run it continues: seed and row0 come from the state, and an argument
+            # that names another one (anything but the default 0) is a mistake, not a request
+            if (seed64 != 0 and seed64 != seed_s) or (row0 != 0 and row0 != row0_s):
+                raise ValueError('init is the state of a run with seed %d and row0 %d: leave seed and row0 out or pass the same' % (seed_s, row0_s))
+            seed64, row0 = seed_s, row0_s
+        if draw is not None:
+            draw0 = int(draw)
+        else:
+            draw0 = last if cont else self._draws
+        if draw0 < 0 or draw0 + steps >= 2 ** 31:
+            raise ValueError('the draws draw0 .. draw0 + steps must lie in [0, 2^31)')
+        if init is not None and not cont:
+            init = np.asarray(init, dtype=float)
+            if init.shape != (N, ncols):
+                raise ValueError('init must be a %d x %d array or the state of an earlier run' % (N, ncols))
+        XsP = self._cols(d, N, zero=True) if Xs is None else Xs
+        if (not isinstance(XsP, torch.Tensor) or XsP.dim() != 2 or XsP.shape[0] != d or XsP.shape[1] < N or XsP.shape[1] & 1
+                or XsP.dtype != torch.float64 or XsP.device.type != self._dev.type or not XsP.is_contiguous()):
+            raise ValueError('Xs must be a contiguous (%d, even width >= %d) matrix of doubles on the device' % (d, N))
+        ldp = XsP.shape[1]                               # (any such width: the state below has its own leading dimension ld)
+        if draw is None:
+            self._draws = max(self._draws, draw0 + steps + 1)
+        coef = self._pack_coeffs()
+        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
+        g_scale = None
+        if self.standardize_samples:
+            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:d]))
+        const = 0.5 * ncols * np.log(2 * np.pi)
+        st = self._stream()
+
+        def weigh(logq):
+            """log p - log q of the rows in XsP"""
+            raw = XsP[c0:d, :N]
+            if self.standardize_samples:                 # (what ttm_export computes: x * sd + mean, two roundings)
+                raw = raw * self._std_d[c0:d, None] + self._mean_d[c0:d, None]
+            logp = log_target_pdf(raw)
+            if not isinstance(logp, torch.Tensor) or logp.numel() != N:
+                raise ValueError('log_target_pdf must return a tensor of %d values' % N)
+            return (logp.reshape(N).to(device=self._dev, dtype=torch.float64) - (logq[:N] - const)).contiguous()
+
+        logq = self._empty(N)
+        if cont:
+            Zcur, Xcur, logw = init['Z'].clone(), init['X'].clone(), init['logw'].clone()
+            n_acc, n_bad = init['n_acc'].clone(), init['n_bad'].clone()
+        else:
+            if init is not None:
+                init_d = self._to_dev(init)              # (held by name: a temporary would be freed before the import reads it)
+                _capi.check(self._lib.ttm_import(self._ptr(init_d), N, ncols, self._ptr(self._mean_d, c0) if self.standardize_samples else None,
+                                                 self._ptr(self._std_d, c0) if self.standardize_samples else None, self._ptr(XsP, c0 * ldp), ldp, st))
+                Zcur = self._cols(ncols, N)
+                logdet, sumsq = self._empty(N), self._empty(N)
+                sigma = None if g_scale is None else torch.reciprocal(g_scale)
+                _capi.check(self._lib.ttm_forward(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), self._ptr(XsP), ldp, N, k0, self.D,
+                                                  self._ptr(Zcur), ld, self._ptr(logdet), self._ptr(sigma), self._ptr(sumsq), st))
+                logq.copy_(logdet - 0.5 * sumsq)
+            else:
+                Zcur = self.reference_device(N, seed=seed, draw=draw0, ncols=ncols, col0=k0, row0=row0)
+                self._inverse_logq(coef, k0, self.D, Zcur, XsP, N, table, logq, g_scale)
+            Xcur = self._cols(ncols, N, zero=True)       # (its own matrix of leading dimension ld, whatever the width of Xs)
+            Xcur[:, :N].copy_(XsP[c0:d, :N])
+            logw = weigh(logq)
+            if bool((torch.isnan(logw) | (logw == float('inf'))).any().item()):       # (the one read-back of the run)
+                raise ValueError('an initial log-weight is NaN or +inf')
+            n_acc, n_bad, done = self._zeros(N, dtype=torch.int32), self._zeros(N, dtype=torch.int32), 0
+        Zp = (self._cols(ncols, N), self._cols(ncols, N))
+        lw = [logw, self._empty(N)]
+        lwp = None
+        trace = self._empty(kept, ncols, ld)
+        for t in range(steps + 1):
+            accept, propose = t >= 1, t < steps
+            rec = trace[(t - burn) // thin - 1] if (accept and t > burn and (t - burn) % thin == 0) else None
+            zn = Zp[t & 1] if propose else None
+            _capi.check(self._lib.ttm_mh_step(self._ptr(Zcur), ld, self._ptr(Xcur), ld, self._ptr(lw[0]), self._ptr(lw[1]) if accept else None,
+                                              self._ptr(Zp[(t - 1) & 1]) if accept else None, ld, self._ptr(XsP, c0 * ldp) if accept else None, ldp,
+                                              self._ptr(lwp) if accept else None, self._ptr(zn), ld, rho, self._ptr(rec), ld,
+                                              self._ptr(n_acc), self._ptr(n_bad), N, ncols, k0, seed64, draw0 + t if accept else 0,
+                                              draw0 + t + 1 if propose else 0, row0, st))
+            if accept:
+                lw.reverse()
+            if propose:
+                self._inverse_logq(coef, k0, self.D, zn, XsP, N, table, logq, g_scale)
+                lwp = weigh(logq)
+        state = dict(Z=Zcur, X=Xcur, logw=lw[0], n_acc=n_acc, n_bad=n_bad, steps=done + steps, draws=(draw0, draw0 + steps),
+                     seed=seed64, row0=row0)
+        return trace, state
+
+    def sample_mcmc(self, log_target_pdf, chains, steps, X_star=None, rho=0.0, burn=0, thin=1, seed=0, draw=None, row0=0, init=None,
+                    target_on_device=False):
+        """Map-preconditioned Metropolis-Hastings (mcmc_device, which states the algorithm and the draw numbers): `chains`
+        independent chains, one per row, of `steps` steps towards the density exp(log_target_pdf), with the fitted map as the
+        preconditioner - where importance resampling (sample_importance) loses its effective sample size to a mediocre fit, a
+        chain with rho near 1 still moves.  Returns (X, info): X a (kept, chains, D - k0) array of raw coordinates, the own
+        columns of the states after the steps burn + thin, burn + 2 thin, ... <= steps (k0: the first inverted component).
+        X_star: the conditioning shapes of sample(), one point for all rows included.  log_target_pdf gets the raw own
+        coordinates of all chains as a chains x (D - k0) NumPy array and returns `chains` values (the convention of
+        sample_importance; it may be unnormalised); target_on_device True: a (D - k0, chains) device tensor in, a device tensor
+        out - then nothing but the kept trace crosses PCIe.  rho, seed, draw, row0, init: as mcmc_device; the initial state is
+        sample(chains, X_star, seed, draw0, row0, logdensity=True) and its weight, bit for bit, and with rho = 0 the proposal of
+        step t is sample(chains, X_star, seed, draw0 + t, row0).
+        info: 'accept_rate' (chains,) accepted steps / steps (over all runs that `state` continues), 'n_bad' (chains,) proposals
+        whose weight was NaN or +inf (rejected), 'logw' the log-weights of the final states, 'draws' (draw0, draw0 + steps),
+        'state' what init= takes to continue the run to the bits of one longer run.
+        ValueError: chains, steps or thin < 1, burn < 0, no kept state, |rho| >= 1, draw0 + steps >= 2^31, an init of the wrong
+        shape or a state that is incomplete or continued with another seed or row0 than its own, a target that does not return
+        `chains` values, an initial log-weight that is NaN or +inf (-inf is allowed: such a chain accepts its first admissible
+        proposal).
+        With the table inverse the chain targets the density up to the table's round-trip error; see mcmc_device."""
+        N = int(chains)
+        if N < 1:
+            raise ValueError('chains must be at least 1')
+        k0, E, Xstar_cols = self._conditioning(X_star)
+        one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
+        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
+        ncols = self.D - k0
+        target = log_target_pdf
+        if not target_on_device:
+            def target(raw):
+                logp = np.asarray(log_target_pdf(np.ascontiguousarray(raw.cpu().numpy().T)), dtype=float).reshape(-1)
+                if logp.shape[0] != N:
+                    raise ValueError('log_target_pdf must return %d values' % N)
+                return self._to_dev(logp)
+        trace, state = self.mcmc_device(target, N, steps, Xs=Xs, rho=rho, burn=burn, thin=thin, seed=seed, draw=draw, row0=row0, init=init, k0=k0)
+        kept, c0 = trace.shape[0], self._cm.d_cols - ncols
+        out = self._empty(kept, N, ncols)
+        mean = self._ptr(self._mean_d, c0) if self.standardize_samples else None
+        sd = self._ptr(self._std_d, c0) if self.standardize_samples else None
+        for i in range(kept):
+            _capi.check(self._lib.ttm_export(self._ptr(trace[i]), trace.shape[2], N, 0, ncols, mean, sd, self._ptr(out[i]), self._stream()))
+        info = dict(accept_rate=state['n_acc'].cpu().numpy() / float(state['steps']), n_bad=state['n_bad'].cpu().numpy(),
+                    logw=state['logw'].cpu().numpy(), draws=state['draws'], state=state)
+        return out.cpu().numpy(), info
+
     def _inverse_table(self, coef, k0, k1, Zs, Xs, N, resolution=1001, start_distance=10, row0=0):
         """TM:3987-4084 for all components: tabulate, index and look up on the device.  interp1d sorts its
         abscissae (stable) first; monotone tables are already sorted, which the index kernel verifies -
