@@ -8,7 +8,13 @@ import numpy as np
 import pytest
 
 from tests.hostemu import emu
-from tests.util import case_X, coeff_lists, ctor_kwargs, load_case, make_oracle
+from tests.util import case_X, coeff_lists, ctor_kwargs, load_case, make_oracle, record_parity
+
+
+def record(backend, name, what, value):
+    """The share actually reached, next to the other run artefacts (device runs; tests/util.py: record_parity)."""
+    if backend == 'hip':
+        record_parity('newton_inverse/%s/%s' % (name, what), value)
 
 
 @pytest.fixture(params=[pytest.param('hostemu'), pytest.param('hip', marks=pytest.mark.gpu)])
@@ -38,20 +44,30 @@ def test_newton_finds_the_reference_roots(backend, name):
     # the reference's own result may have run away (targets beyond a component's range: |x| ~ 1e8); compare where it did not
     sane = np.all(np.abs(ref) < 50.0, axis=1)
     sane[0] = False                                                     # (sample 0 of the reference: loop-guard quirk)
+    print('%s %s: sane share %.4f (> 0.8; a figure of the golden alone)' % (name, backend, sane.mean()))
     assert sane.mean() > 0.8
     skipcols = np.zeros((len(got), om.skip_dimensions)) + om.X_mean[:om.skip_dimensions]
     res = np.abs(om.map(np.column_stack((skipcols, got))) - Zin)
     assert res[sane].max() < 2e-9                                       # the stopping rule, under the oracle's forward map
     # positions: both stop at |S - z| <= 1e-9, so they differ by <= 2e-9 / (dS/dx): 1e-6 covers slopes down to 2e-3
     close = np.abs(got[sane] - ref[sane]) <= 1e-6 * (1 + np.abs(ref[sane]))
+    print('%s %s: close share %.6f (> 0.98; reached 1.0), %d of %d' % (name, backend, close.mean(), int(close.sum()), close.size))
+    record(backend, name, 'sane_share', sane.mean())
+    record(backend, name, 'close_share', close.mean())
     assert close.mean() > 0.98
+    assert close.all()                              # (the share the host double reaches on every case here: 1.0)
     # conditional inversion (X_star) where the fixture has it
     if name == 'misc_grid':
         gotc = tm.inverse_map(Zin, X_star=npz['inv_Xstar'])
         refc = npz['inv_X']
         sane = np.all(np.abs(refc) < 50.0, axis=1)
         sane[0] = False
-        assert (np.abs(gotc[sane] - refc[sane]) <= 1e-6 * (1 + np.abs(refc[sane]))).mean() > 0.98
+        closec = np.abs(gotc[sane] - refc[sane]) <= 1e-6 * (1 + np.abs(refc[sane]))
+        print('%s %s conditional: sane share %.4f, close share %.6f (> 0.98; reached 1.0)' % (name, backend, sane.mean(), closec.mean()))
+        record(backend, name, 'conditional_sane_share', sane.mean())
+        record(backend, name, 'conditional_close_share', closec.mean())
+        assert closec.mean() > 0.98
+        assert closec.all()
 
 
 def test_newton_needs_fewer_trial_points(backend):
