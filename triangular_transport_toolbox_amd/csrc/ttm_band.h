@@ -33,18 +33,20 @@ bool usable(const ttm_program* p, int k0, int k1);
 
 // forward map of the components [k0, k1): Z and / or the fused log-determinant and sum of squares (`block` > 0: at most that
 // many components' splines resident at a time; `resident`: option band_resident - the cache policy of k_band_forward's column
-// streams, csrc/ttm_band_policy.h)
+// streams, csrc/ttm_band_policy.h; `full_tiles`: option band_full_tiles - the cut of a k_band_forward launch, as inverse()'s)
 int forward(const ttm_program* p, const double* U, int k0, int k1, const double* Xsoa, int64_t ldx, int64_t N, double* Zsoa,
-            int64_t ldz, double* logdet, const double* sigma, double* sumsq, int cus, size_t lds_per_cu, int block, int resident, void* stream,
-            const char** kernel_name);
+            int64_t ldz, double* logdet, const double* sigma, double* sumsq, int cus, size_t lds_per_cu, int block, int resident, int full_tiles,
+            void* stream, const char** kernel_name);
 
 // table inverse (resident windowed tables, as k_inverse_rt) in push form
 // img: the resident-table images of the components (image_plan; written by k_table_build_index) or nullptr
 // resident: option band_resident - the cache policy of k_band_inverse_ring's column streams (csrc/ttm_band_policy.h)
+// full_tiles, zdma, ring_slots: options band_full_tiles, band_zdma, band_ring_slots - the cut of a k_band_inverse_ring launch, its
+// ZD and the slots of its ring (same header)
 int inverse(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx,
             int64_t N, const double* tab_x, int T, const double* y_affine, const double* tmin, const double* tmax, const int32_t* bkt,
-            int nb, const double* img, int img_doubles, int cus, size_t lds_per_cu, int window, int block, int resident, void* stream,
-            const char** kernel_name);
+            int nb, const double* img, int img_doubles, int cus, size_t lds_per_cu, int window, int block, int resident, int full_tiles, int zdma,
+            int ring_slots, void* stream, const char** kernel_name);
 
 // safeguarded Newton root search (sample_newton, csrc/ttm_eval.h: bracket +-2, window doubling, |S - z| <= 1e-9, at most 100
 // trial points) in push form: the monotone part is the component's resident spline (+ its linear own term), no

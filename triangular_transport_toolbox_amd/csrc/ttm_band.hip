@@ -58,6 +58,10 @@ static_assert(BAND_POLICY_TILE_ROWS == BAND_NS * BAND_CT && BAND_POLICY_HALF_ROW
 __device__ __forceinline__ void band_dma16(const void* g, unsigned int lds_wave_base) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(lds_wave_base) : "m0");
 }
+// ... with the non-temporal bit (the column stream of Z that is not to stay on-die: band_z_nt)
+__device__ __forceinline__ void band_dma16_nt(const void* g, unsigned int lds_wave_base) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" ::"v"(g), "s"(lds_wave_base) : "m0");
+}
 __device__ __forceinline__ unsigned int band_lds_addr(const void* p) {
     return (unsigned int)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
@@ -1204,10 +1208,25 @@ __device__ __forceinline__ void band_ring_fill(const double* img, int ncomp, dou
 
 // POL = 1 (the ring kernel only): Z is loaded plainly in pair slot 0 and non-temporally in slot 1 (band_z_nt), X stored
 // non-temporally; a partial tile's single rows, the DMA pieces and the outlier path's table reads stay plain
-template <int CLS, int LAG, bool RING = false, int G = 0, int POL = 0>
+//
+// ZD = 1 (the ring kernel beside POL = 1, FULL tiles only - the caller passes full = true): Z travels through LDS, two columns
+// deep.  Every wave owns 2 KB of each of two column buffers (zq: the LDS address of its part of buffer 0; BAND_ZD_BUF bytes
+// on, buffer 1); column c of the tile lives in buffer (c - kb) & 1.  Step j finds column j in registers, requests column
+// j + 2 by two DMA instructions into the buffer column j came from, waits - a COUNTED wait - for column j + 1, requested a
+// step ago, and reads it back: each lane the very 16-byte units its own DMA lanes wrote, so no other wave is involved and no
+// barrier.  The caller has requested columns kb and kb + 1 and waited for them.  Past the last column the requests are
+// harmless repeats, so that every step puts the same number of operations behind the one it waits for.
+#define BAND_ZD_BUF (BAND_NS * BAND_CT * 8)          /* bytes of a column buffer: a tile's rows of one column */
+static_assert(2 * BAND_ZD_BUF == BAND_ZDMA_LDS_BYTES, "ttm_band_policy.h counts the LDS of these two buffers");
+template <int POL, int Q>
+__device__ __forceinline__ void band_zd_request(const char* g, unsigned int lds_wave_base) {
+    if (band_z_nt<POL, Q>) band_dma16_nt(g, lds_wave_base); else band_dma16(g, lds_wave_base);
+}
+template <int CLS, int LAG, bool RING = false, int G = 0, int POL = 0, int ZD = 0>
 __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool full, int kb, int ke, const char* zcol, char* xcol, unsigned int tbase,
                                                   const unsigned int (&roff)[BAND_NS / 2], double (&pend)[BAND_NS][LAG],
-                                                  const D2 (&zfirst)[BAND_NS / 2], bool have_first, BandRing* rg = nullptr) {
+                                                  const D2 (&zfirst)[BAND_NS / 2], bool have_first, BandRing* rg = nullptr, unsigned int zq = 0) {
+    static_assert(ZD == 0 || (RING && POL == 1), "ZD = 1: the ring kernel under the resident policy");
     constexpr int DB = cls_db(CLS), DA = cls_da(CLS), PS = rec_stride(CLS, LAG);
     constexpr int NS = BAND_NS, NP = NS / 2, HALF = 2 * BAND_CT;
     cdbl_p rec = cx.P + (int64_t)(kb + LAG) * PS;
@@ -1216,7 +1235,19 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
     const double ystep = cx.ystep;
     const int nb1 = cx.nb - 1;
     D2 za[NP], zb[NP];
-    if (have_first) {                                         // (the chunk's first tile: requested before the block's tables)
+    // (ZD) this lane's unit of the wave's part of buffer 0, formed where it is used: three instructions the compiler cannot hoist.
+    // Kept across the step it is one VGPR too many - spilled, and its reload, a vector-memory load the compiler counts, put
+    // a wait in front of the read-back that drained the column requested a moment before
+    auto zrd = [&]() {
+        unsigned int a;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshl_add_u32 %0, %0, 4, %1" : "=&v"(a) : "s"(zq));
+        return (lds_p)(uintptr_t)a;
+    };
+    if (ZD) {                                                 // (column kb has landed in buffer 0: the caller waited)
+#pragma unroll
+        for (int q = 0; q < NP; ++q) za[q] = band_lds_pair(zrd() + q * 1024);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    } else if (have_first) {                                         // (the chunk's first tile: requested before the block's tables)
 #pragma unroll
         for (int q = 0; q < NP; ++q) za[q] = zfirst[q];
     } else {
@@ -1239,8 +1270,15 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
         p = fma(p, w, 1.0);
         ee = e_lo * p;
     };
-    auto step = [&](int j, const D2 (&zc)[NP], D2 (&zn)[NP]) {
-        {
+    auto step = [&](int j, const D2 (&zc)[NP], D2 (&zn)[NP], int par) {  // par: (j - kb) & 1 (ZD)
+        if (ZD) {
+            // column j + 2 into the buffer column j was read from (the reads have retired: lgkmcnt(0) at the end of the last step)
+            const char* zreq = zcol + (j + 2 < ke ? 2 * cx.ldzb : j + 1 < ke ? cx.ldzb : 0);
+            band_slots<NP>([&](auto Q) {
+                constexpr int q = decltype(Q)::value;
+                band_zd_request<POL, q>(zreq + roff[q], zq + (unsigned int)(par * BAND_ZD_BUF + q * 1024));
+            });
+        } else {
             const char* znext = j + 1 < ke ? zcol + cx.ldzb : zcol;           // (past the block: a harmless re-read)
             band_slots<NP>([&](auto Q) { constexpr int q = decltype(Q)::value; zn[q] = band_load2<band_z_nt<POL, q>>(znext + roff[q]); });
         }
@@ -1274,6 +1312,18 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
             band_dma16(rg->src + (size_t)rg->tcomp * rg->stride, rg->tabs_lds + (unsigned int)rg->tpos * rg->stride + rg->dst);
             if (++rg->tpos == rg->R) rg->tpos = 0;
             if (++rg->tcomp == rg->ncomp) rg->tcomp = 0;
+        }
+        if (ZD) {
+            // column j + 1, requested at the top of the last step (or by the caller): behind its two requests stand that step's
+            // piece and two stores and this step's two requests and piece - a full tile's step issues every one of them
+            // unconditionally (an outlier path's loads in between only make the wait stricter)
+            constexpr int PIECE = G > 0 ? 1 : 0, BEHIND = (PIECE + 2) + (2 + PIECE);   // last step: piece, stores; this one: requests, piece
+            static_assert(BEHIND == (G > 0 ? 6 : 4), "the literal of the counted wait below");
+            if (G > 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            const lds_p zr = zrd();
+#pragma unroll
+            for (int q = 0; q < NP; ++q) zn[q] = band_lds_pair(zr + ((par ^ 1) * BAND_ZD_BUF + q * 1024));
         }
         // the four rows in phases, so that their dependent LDS reads travel together: bucket -> the bucket's entries ->
         // the interval.  np.searchsorted(xs, target) (left) = entries in lower buckets + entries of the target's own
@@ -1353,23 +1403,26 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
             }
         }
         rec += PS; slot += cx.tab_slot; zcol += cx.ldzb; xcol += cx.ldxb;
+        if (ZD) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // (the next step's request overwrites what was just read)
         if (RING) {
             if (++rg->pos == rg->R) { rg->pos = 0; slot = cx.tabs; }
             if (G > 0 && ++rg->gcnt == G) {
                 rg->gcnt = 0;
                 // this wave's pieces from before the last meeting have landed: every step since put two column loads and a piece behind them
-                static_assert(G == 0 || G == 4, "the counted wait below is 3 G - 2");
-                asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+                // (ZD: five operations per step - two requests, the piece, two stores - and the last step's stores: 5 G + 2)
+                static_assert(G == 0 || (3 * G - 2 == 10 && (2 + 1 + 2) * G + 2 == 22), "the literals of the counted waits below: 3 G - 2 and 5 G + 2");
+                if (ZD) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
                 __syncthreads();
             }
         }
     };
     int j = kb;
     for (; j + 1 < ke; j += 2) {
-        step(j, za, zb);
-        step(j + 1, zb, za);
+        step(j, za, zb, 0);
+        step(j + 1, zb, za, 1);
     }
-    if (j < ke) step(j, za, zb);
+    if (j < ke) step(j, za, zb, 0);
 }
 
 // KM: components per block, at most (what the table load is unrolled for: 4 for maps of a few components, BAND_RT_KMAX)
@@ -1551,7 +1604,9 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse(const double* __restri
 // row does not depend on the chunking (k_band_inverse re-reads LAG columns at a block boundary when a chunk has several tiles
 // and takes their exp(-x^2/4) from the series there).  The step itself is band_inverse_tile, shared with k_band_inverse.
 // POL: the cache policy of the column streams (band_inverse_tile; the host's choice: ttm_band_policy.h)
-template <int CLS, int LAG, int G, int POL = 0>
+// ZD = 1: full tiles take Z through two column buffers in LDS behind the {E_i, y_i} pairs (band_inverse_tile; the ring has
+// fewer slots: band_ring_plan_with), partial tiles run the code of ZD = 0
+template <int CLS, int LAG, int G, int POL = 0, int ZD = 0>
 __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                                const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
                                                                const double* __restrict__ tab_x, int T, double y0, double ystep, double ylast,
@@ -1592,8 +1647,26 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
         rg.tpos = G > 0 ? R - G : 0;
         rg.tcomp = G > 0 ? (R - G) % ncomp : 0;
     }
+    // (ZD) this wave's 2 KB of column buffer 0, as an LDS address
+    const unsigned int zq = ZD ? __builtin_amdgcn_readfirstlane(band_lds_addr(etab + 2 * Weven) + (unsigned int)(tid >> 6) * 2048u) : 0u;
+    // a full tile's first two columns of z into the column buffers (ZD); the tile's rows are below N: no clamp
+    auto zd_request2 = [&](int tile) {
+        band_slots<NP>([&](auto Q) {
+            constexpr int q = decltype(Q)::value;
+            const unsigned int n = (unsigned int)c0 + (unsigned int)tile * (unsigned int)ROWS + 2u * (unsigned int)tid + (unsigned int)(q * HALF);
+            const char* g = (const char*)Z + (size_t)(n * 8u);
+            band_zd_request<POL, q>(g, zq + (unsigned int)(q * 1024));
+            band_zd_request<POL, q>(k0 + 1 < k1 ? g + ldzb : g, zq + (unsigned int)(BAND_ZD_BUF + q * 1024));
+        });
+    };
+    const bool zd0 = ZD != 0 && c0 + ROWS <= c1;               // (the first tile is full and takes z through LDS)
     // the first column of z of the first tile, then the images of the first R steps: one memory round trip
     D2 zfirst[NP];
+    if (zd0) {
+        zd_request2(0);
+#pragma unroll
+        for (int q = 0; q < NP; ++q) zfirst[q] = D2{0.0, 0.0};
+    } else
     band_slots<NP>([&](auto Q) {
         constexpr int q = decltype(Q)::value;
         unsigned int n = (unsigned int)c0 + 2u * (unsigned int)tid + (unsigned int)(q * HALF);
@@ -1617,6 +1690,12 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
             n = n < last_pair ? n : last_pair;
             roff[q] = n * 8u;
         }
+        if (ZD && full && tile > 0) {
+            // the last tile's trailing requests have landed before the buffers are requested into again; the wait for these two
+            // columns stands behind the running sums below
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            zd_request2(tile);
+        }
         // running sums at the first column from the LAG columns in front of it (conditioning columns, or nothing)
         double pend[NS][LAG];
 #pragma unroll
@@ -1635,6 +1714,12 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
                 band_push<DB, DA, LAG>(rec + TTM_P_HDR, rec[1], xv.y, cc >= 0 ? band_expq_series(xv.y) : 1.0, pend[2 * q + 1]);
             }
         }
+        if (ZD && full) {
+            if constexpr (ZD != 0) {
+                if (tile > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                band_inverse_tile<CLS, LAG, true, G, POL, 1>(cx, true, k0, k1, (const char*)Z, (char*)X + (int64_t)kcol0 * ldxb, tbase, roff, pend, zfirst, false, &rg, zq);
+            }
+        } else
         band_inverse_tile<CLS, LAG, true, G, POL>(cx, full, k0, k1, (const char*)Z, (char*)X + (int64_t)kcol0 * ldxb, tbase, roff, pend, zfirst, tile == 0, &rg);
     }
 }
@@ -3032,15 +3117,13 @@ static bool y_affine_ok(const double* y) {
 // rows of a workgroup's chunk: N / #CUs rounded up to whole 128-byte lines of a column, so that every wave's 1 KB
 // accesses are line-aligned (a chunk that starts inside a line makes every wave's store touch nine lines, two of them
 // partially: the column stream then runs at 72 % of the copy rate instead of ...: profiles/r03_*)
-static int64_t chunk_rows(int64_t N, int cus) {
-    const int64_t rows = (N + cus - 1) / cus;
-    return (rows + 31) / 32 * 32;
-}
+static int64_t chunk_rows(int64_t N, int cus) { return band_policy_chunk_rows(N, cus); }
 struct ChunkGrid { int64_t rows, grid; };            // the long kernels: one chunk of rows per workgroup
 static ChunkGrid chunk_grid(int64_t N, int cus) {
     const int64_t rows = chunk_rows(N, cus);
     return {rows, (N + rows - 1) / rows};
 }
+// k_band_forward and k_band_inverse_ring: whole tiles where they keep the CUs busy (band_policy_cut), else the cut above
 
 int record_stride(int cls, int lag) { return rec_stride(cls, lag); }
 
@@ -3145,8 +3228,8 @@ static size_t block_lds_span(const ttm_program* p, int k0, int k1, int Bc, bool 
 }
 
 int forward(const ttm_program* p, const double* U, int k0, int k1, const double* Xsoa, int64_t ldx, int64_t N, double* Zsoa, int64_t ldz,
-            double* logdet, const double* sigma, double* sumsq, int cus, size_t lds_per_cu, int block, int resident, void* stream,
-            const char** kernel_name) {
+            double* logdet, const double* sigma, double* sumsq, int cus, size_t lds_per_cu, int block, int resident, int full_tiles,
+            void* stream, const char** kernel_name) {
     // (rows: 2^28 here, 2^29 at the gate in ttm_kernels.hip - both stand)
     if (!usable(p, k0, k1) || (!Zsoa && !logdet && !sumsq) || N >= ((int64_t)1 << 28)) return 1;
     // (need = 0 for Z: ldz is not held against N here, as it is in roundtrip() and newton())
@@ -3206,13 +3289,14 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
                       sumsq, cg.rows, Bc);
     }
     // the cache policy of the column streams (ttm_band_policy.h): a function of the sizes, or the option's
-    const bool pol = (band_resident_policy(N, cg.rows, k1 - k0, resident) & BAND_POLICY_FORWARD) != 0;
+    const BandCut lc = band_policy_cut(N, cus, full_tiles);   // (whole tiles where they keep the CUs busy, else cg)
+    const bool pol = (band_resident_policy(N, lc.rows, k1 - k0, resident) & BAND_POLICY_FORWARD) != 0;
     auto kern = with_bool(pol, [&](auto PO) {
         return with_bool(own, [&](auto OW) {
             return with_cls<3>(cls, [&](auto C) { return k_band_forward<decltype(C)::value, 2, decltype(OW)::value, decltype(PO)::value ? 1 : 0>; });
         });
     });
-    return launch(kern, cg.grid, lds, stream, "k_band_forward", kernel_name, U, p->u_p_off, k0, k1, kcol0, Xsoa, ldx, N, Zsoa, ldz, cg.rows, Bc);
+    return launch(kern, lc.grid, lds, stream, "k_band_forward", kernel_name, U, p->u_p_off, k0, k1, kcol0, Xsoa, ldx, N, Zsoa, ldz, lc.rows, Bc);
 }
 
 // forward (+ density terms) + table inverse of a map of a few components in one launch (k_band_few_roundtrip); 1: not for this map /
@@ -3334,7 +3418,8 @@ static BlockPlan block_plan(int T, int W, int nb, int ncomp, size_t lds_per_cu, 
 // table inverse, in this order: the few-component kernel, the ring kernel (images at hand, laid out for this very plan), the block kernel
 int inverse(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
             const double* tab_x, int T, const double* y_affine, const double* tmin, const double* tmax, const int32_t* bkt, int nb, const double* img,
-            int img_doubles, int cus, size_t lds_per_cu, int window, int block, int resident, void* stream, const char** kernel_name) {
+            int img_doubles, int cus, size_t lds_per_cu, int window, int block, int resident, int full_tiles, int zdma, int ring_slots,
+            void* stream, const char** kernel_name) {
     if (!usable(p, k0, k1) || T < 64 || T > 4096 || nb + 1 != 1024 || N >= ((int64_t)1 << 28)) return 1;      // (bucket rows copied 16 bytes at a time, 256 units per row)
     if (!vec_ok(bkt) || !y_affine_ok(y_affine)) return 1;
     if (!col_ok(Zsoa, ldz, even_rows(N)) || !col_ok(Xsoa, ldx, even_rows(N))) return 1;
@@ -3362,16 +3447,19 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
     BandRingPlan pl;
     if (img && vec_ok(img) && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl) &&
         pl.tab_slot == img_doubles) {                         // (laid out for another plan - options changed in between: not this kernel)
-        const bool pol = (band_resident_policy(N, cg.rows, ncomp, resident) & BAND_POLICY_INVERSE) != 0;      // (as forward())
-        auto rk = with_bool(pol, [&](auto PO) {
-            return with_bool(pl.G == 4, [&](auto G4) {
-                return with_cls<3>(cls, [&](auto C) {
-                    return k_band_inverse_ring<decltype(C)::value, 2, decltype(G4)::value ? 4 : 0, decltype(PO)::value ? 1 : 0>;
-                });
+        // the cut (as forward()), the cache policy, ZD and the slots of the ring: band_ring_launch, ttm_band_image.h
+        const BandRingLaunch rl = band_ring_launch(pl, N, cus, ncomp, lds_per_cu, full_tiles, resident, zdma, ring_slots);
+        const BandCut lc = rl.cut;
+        const bool pol = rl.pol, zd = rl.zd;
+        pl = rl.ring;
+        auto rk = with_bool(pl.G == 4, [&](auto G4) {
+            return with_cls<3>(cls, [&](auto C) {
+                constexpr int CL = decltype(C)::value, GG = decltype(G4)::value ? 4 : 0;
+                return zd ? k_band_inverse_ring<CL, 2, GG, 1, 1> : pol ? k_band_inverse_ring<CL, 2, GG, 1> : k_band_inverse_ring<CL, 2, GG>;
             });
         });
-        return launch(rk, cg.grid, pl.lds, stream, "k_band_inverse_ring", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, tab_x, T,
-                      y_affine[0], y_affine[1], y_affine[2], tmin, tmax, img, nb, pl.tab_slot, pl.R, cg.rows, pl.w0, pl.W);
+        return launch(rk, lc.grid, pl.lds, stream, "k_band_inverse_ring", kernel_name, U, p->u_p_off, k0, k1, kcol0, Zsoa, ldz, Xsoa, ldx, N, tab_x, T,
+                      y_affine[0], y_affine[1], y_affine[2], tmin, tmax, img, nb, pl.tab_slot, pl.R, lc.rows, pl.w0, pl.W);
     }
     BlockPlan b = block_plan(T, T, nb, ncomp, lds_per_cu, block);
     // windowed tables when that saves a pass over the chunk (k_inverse_rt): on request (window > 0: whenever they fit), or by

@@ -15,6 +15,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ttm_band_policy.h"
+
 #define BAND_RT_HDR 6
 #define BAND_RING_KMAX 24                             /* slots of the ring, at most */
 
@@ -70,6 +72,48 @@ static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, i
     }
     pl->lds = slot.lds(pl->R);
     return true;
+}
+
+// The plan `pl` with `extra` bytes of LDS behind the {E_i, y_i} pairs (the column buffers of k_band_inverse_ring's ZD = 1)
+// and at most `max_slots` slots (0: as many as fit): the SAME images - window and doubles per image are what the table
+// kernel wrote - in a ring of fewer slots.  A ring without refill keeps every component whatever `max_slots`.  false: the
+// slots left are fewer than the ring needs (every component when there is no refill, else the 3 G of band_ring_plan).
+static inline bool band_ring_plan_with(const BandRingPlan& pl, size_t lds_per_cu, size_t extra, int max_slots, BandRingPlan* out) {
+    const BandImageSlot slot = {pl.Weven, pl.tab_slot};
+    if (slot.lds(0) + extra > lds_per_cu) return false;
+    const int B = (int)((lds_per_cu - extra - slot.lds(0)) / ((size_t)slot.tab_slot * 8));
+    *out = pl;
+    if (pl.G == 0) { if (B < pl.R) return false; }
+    else {
+        int R = (B < pl.R ? B : pl.R) / pl.G * pl.G;       // what fits
+        if (R < 3 * pl.G) return false;
+        if (max_slots > 0 && max_slots < R) R = (max_slots < 3 * pl.G ? 3 * pl.G : max_slots) / pl.G * pl.G;   // (a cap only lowers it, to 3 G at least)
+        out->R = R;
+    }
+    out->lds = slot.lds(out->R) + extra;
+    return true;
+}
+
+// Everything ttm_band::inverse decides about a k_band_inverse_ring launch once the images fit the plan `pl`: the cut, the
+// cache policy, ZD and the ring it launches with.  THE one copy: the host entry point and the CPU program of the tests
+// (tests/band_cut_gate.cpp) both call it.  ring_slots: option band_ring_slots (0 / -1: as many slots as fit).
+struct BandRingLaunch {
+    BandCut cut;
+    bool pol, zd;                                     // POL = 1, ZD = 1
+    BandRingPlan ring;                                // slots and dynamic LDS of the launch
+};
+static inline BandRingLaunch band_ring_launch(const BandRingPlan& pl, int64_t N, int cus, int ncomp, size_t lds_per_cu, int full_tiles,
+                                              int resident, int zdma, int ring_slots) {
+    BandRingLaunch l;
+    l.cut = band_policy_cut(N, cus, full_tiles);
+    l.pol = (band_resident_policy(N, l.cut.rows, ncomp, resident) & BAND_POLICY_INVERSE) != 0;
+    const int slots = ring_slots > 0 ? ring_slots : 0;
+    BandRingPlan with;
+    // Z two columns ahead through LDS: the same images in the slots the two column buffers leave
+    l.zd = band_zdma_policy(N, l.cut, l.pol, band_ring_plan_with(pl, lds_per_cu, (size_t)BAND_ZDMA_LDS_BYTES, slots, &with), zdma);
+    l.ring = pl;
+    if (l.zd || (slots > 0 && band_ring_plan_with(pl, lds_per_cu, 0, slots, &with))) l.ring = with;
+    return l;
 }
 
 #if defined(__HIPCC__)

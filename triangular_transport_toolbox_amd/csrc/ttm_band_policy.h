@@ -36,6 +36,50 @@ static inline int64_t band_policy_resident_rows(int64_t N, int64_t chunk_rows) {
     return whole * of_chunk(chunk_rows) + of_chunk(N - whole * chunk_rows);
 }
 
+// ---- the cut of N rows into one chunk per workgroup (the long kernels) ----
+// today's cut: N / #CUs rows rounded up to whole 128-byte lines of a column, so that every wave's 1 KB accesses are
+// line-aligned (a chunk that starts inside a line makes every wave's store touch nine lines, two of them partially: the
+// column stream then runs at 72 % of the copy rate: profiles/r03_*)
+struct BandCut { int64_t rows, grid; bool full_tiles; };    // full_tiles: the rule below chose the cut
+static inline int64_t band_policy_chunk_rows(int64_t N, int cus) {
+    const int64_t rows = (N + cus - 1) / cus;
+    return (rows + 31) / 32 * 32;
+}
+// option band_full_tiles (ttm_options.h): -1 auto, 0 off, 1 wherever whole tiles give every CU at most one chunk.
+// k_band_forward and k_band_inverse_ring (both take THIS cut: the resident half of Z is defined by it) walk a full tile in
+// a column loop of straight-line code with counted waits and a partial one in a masked loop that drains its loads at every
+// loop-back.  Today's cut gives C5 at N = 1e6 on 256 CUs chunks of 3 936 rows: no workgroup has a full tile.  Chunks of one
+// whole tile - ceil(N / 4096) workgroups, all but the last with a full tile - when that leaves at most 1 / 16 of the CUs
+// without work: 1e6 rows -> 245 workgroups of 4 096 rows (OPTLOG round 15).
+static inline BandCut band_policy_cut(int64_t N, int cus, int option) {
+    if (cus < 1) cus = 1;
+    const int64_t tiles = (N + BAND_POLICY_TILE_ROWS - 1) / BAND_POLICY_TILE_ROWS;
+    const bool fits = N > 0 && tiles <= cus;
+    if (option != 0 && fits && (option > 0 || tiles >= cus - cus / 16)) return {BAND_POLICY_TILE_ROWS, tiles, true};
+    const int64_t rows = band_policy_chunk_rows(N, cus);
+    return {rows, rows > 0 ? (N + rows - 1) / rows : 0, false};
+}
+
+// ---- Z through LDS, two columns deep (template parameter ZD of k_band_inverse_ring) ----
+// bytes of LDS the two column buffers take: 2 columns x 16 waves x 2 pair slots x 1 KB
+constexpr int64_t BAND_ZDMA_LDS_BYTES = 2 * (int64_t)BAND_POLICY_TILE_ROWS * 8;
+// option band_zdma: -1 auto, 0 off, 1 wherever the kernel can run it.  ZD = 1 exists only beside POL = 1 and acts on full
+// tiles only.  `ring_ok`: the ring keeps enough slots beside the buffers (band_ring_plan_with, ttm_band_image.h).
+// Auto: off.  Measured at C5, N = 1e6, on the whole-tile cut (OPTLOG round 15, two GPUs): the inverse launch 0.1282 / 0.1259 ms
+// against 0.1314 / 0.1269 ms - and 0.1274 / 0.1257 ms with ZD = 0 in the ring of 12 slots that ZD = 1 leaves: what little
+// there is comes from the smaller ring (below), not from the path of z, and the step's ranges overlap.
+static inline bool band_zdma_policy(int64_t N, BandCut cut, bool pol_inverse, bool ring_ok, int option) {
+    if (option <= 0 || !pol_inverse || !ring_ok) return false;
+    return N >= BAND_POLICY_TILE_ROWS && cut.rows >= BAND_POLICY_TILE_ROWS;             // (a full tile somewhere)
+}
+
+// ---- slots of a refilled ring (k_band_inverse_ring, G > 0) ----
+// option band_ring_slots: -1 / 0 as many as fit (24 at C5), > 0 at most that many (whole groups, 3 G at least;
+// band_ring_plan_with).  Every slot is filled in front of the first column - 6 KB each at C5, 150 KB per workgroup before the
+// first row is looked up - while a step needs the images of the next 2 G steps only.  There is no automatic choice: 12 slots
+// were faster than 24 in every comparison of OPTLOG round 15, but never by more than the two ranges added - not a gain by the
+// log's rule.  The option stays as the instrument that tells ZD = 1 from the smaller ring it brings with it.
+
 // option band_resident (ttm_options.h): -1 auto, 0 off, 1 forward only, 2 inverse only, 3 both - 1..3 whatever the size (tests,
 // A/B runs).  Auto is both or none - either half alone moves time from one launch into the other and gave between +1.6 % and
 // -3.6 % on the pair from one GPU to the next, both together -7 % on each (OPTLOG round 12 item 6) - and both when

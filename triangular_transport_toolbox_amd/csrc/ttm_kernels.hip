@@ -3699,7 +3699,7 @@ int ttm_forward(const ttm_program* p, const double* coef, const double* fold, co
         if (band_forward_gate(p, k0, k1, N)) {
             const char* name = nullptr;
             if (ttm_band::forward(p, fold + fold_base_size(p), k0, k1, Xsoa, ldx, N, Zsoa, ldz, logdet, sigma, sumsq, band_cus(),
-                                  device_info().lds_per_cu, tuning().rt_block, tuning().band_resident, stream, &name) == 0)
+                                  device_info().lds_per_cu, tuning().rt_block, tuning().band_resident, tuning().band_full_tiles, stream, &name) == 0)
                 return check_launch(name);
         }
         // large ensembles with aligned columns: loader-wave kernel
@@ -3984,7 +3984,7 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
         const char* name = nullptr;
         if (ttm_band::inverse(p, fold + fold_base_size(p), k0, k1, Zsoa, ldz, Xsoa, ldx, N, tab_x, (int)T, h_y_affine, tmin, tmax, bkt, (int)nb,
                               tn.band_ring != 0 ? img : nullptr, (int)img_doubles, band_cus(), device_info().lds_per_cu, tn.rt_window, tn.rt_block,
-                              tn.band_resident, stream, &name) == 0)
+                              tn.band_resident, tn.band_full_tiles, tn.band_zdma, tn.band_ring_slots, stream, &name) == 0)
             return check_launch(name);
     }
     // k_inverse_rt sweeps the hot records themselves: not for lag-3 maps (include/ttm.h), and with fewer than four
