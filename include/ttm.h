@@ -825,6 +825,30 @@ int ttm_weight_scan(const double* logw, int64_t N, uint64_t* cum, uint64_t* q, t
 int ttm_resample(const uint64_t* cum, int64_t N, int64_t M, int32_t scheme, uint64_t seed, uint32_t draw, const double* Xsoa,
                  int64_t ldx, int32_t ncols, double* Ysoa, int64_t ldy, int32_t* idx, void* stream);
 
+/* ---- the weight summaries of C tempered copies of logw in one pass (no counterpart in the reference) -------------------------
+ * The temperature search of sequential Monte Carlo with adaptive tempering (csrc/ttm_smc.h): the particles
+ * carry their untempered log-weights logw_i = log p - log q, a step of the exponent by delta reweights them by exp(delta logw_i),
+ * and the step is chosen by the effective sample size of many candidates.  For 1 <= N <= 2^30 and 1 <= C <= 64 candidates
+ * delta[c] > 0 (a HOST array, read before the call returns):
+ *   summaries[c] (device) = the four words ttm_weight_scan writes into its summary for the vector v_i = fl(delta[c] * logw_i),
+ *   fl ONE correctly rounded product that is never contracted into the subtraction of the maximum behind it.
+ * m, T and bad agree with that call bit for bit, S2 with that of the same library (the same tree: inside a tile of 1024 rows,
+ * one addition per pass of 256 tiles, then the 256 running sums).  No cum and no q are written.  delta[c] > 0 and rounding is
+ * monotone, so max_i fl(delta[c] logw_i) = fl(delta[c] max_i logw_i): the maximum m of logw is found once and
+ * m_c = fl(delta[c] * m); K = min(40, 62 - ceil(log2 N)) and q_i as above from (v_i, m_c).  NaN and +inf entries count as `bad`
+ * and contribute 0, -inf entries contribute 0; without a valid entry m_c = -inf, T = 0, S2 = 0.  (A product delta[c] * logw_i of
+ * finite factors that overflows is outside the contract: the pre-multiplied vector would hold an infinity there.)
+ * work: caller-owned, device, TTM_TEMPER_SCAN_WORK_WORDS(N, C) words of 8 bytes; it need not be initialised and what it held
+ * does not change any result.  logw, summaries and work must not overlap.  Four launches (k_weight_max, k_weight_max_finish,
+ * k_temper_sums - one workgroup per tile, which loads its rows once and walks the candidates -, k_temper_finish - one workgroup
+ * per candidate), no workgroup waits for another one, no atomics, no host synchronisation, graph-capturable (the candidates are
+ * kernel arguments: a captured graph keeps those of the capture).  Nothing but summaries[0 .. C) and work is written; no
+ * alignment beyond 8 bytes (16-byte loads where a pair of rows is whole and aligned).
+ * TTM_E_ARG: null logw, delta, summaries or work; N < 1 or N > 2^30; C < 1 or C > 64; a delta[c] that is NaN, infinite or <= 0. */
+#define TTM_TEMPER_SCAN_WORK_WORDS(N, C) (4 + (2 + 2 * (int64_t)(C)) * (((N) + 1023) / 1024))
+int ttm_temper_scan(const double* logw, int64_t N, const double* delta, int32_t C, ttm_weight_summary* summaries, void* work,
+                    void* stream);
+
 /* ---- one step of Metropolis-Hastings in the reference space of a fitted map (no counterpart in the reference) --------------
  * N chains, one per row, each with a state z (reference space, ncols own components), its image x = S^-1(z) (standardised own
  * columns) and its log-weight logw = log p(x) - log q(x), all column-major on the device.  The proposal z' = rho z + sqrt(1 -
@@ -863,6 +887,19 @@ int ttm_mh_step(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const do
                 double* Znext, int64_t ldzn, double rho, double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad,
                 int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept, uint32_t draw_propose,
                 int64_t row0, void* stream);
+/* ttm_mh_step_tempered: the same step towards the tempered target q^(1 - beta) p^beta = q w^beta of sequential Monte Carlo, whose
+ * pull-back to the reference space is w(x(z))^beta phi(z).  It differs from ttm_mh_step in ONE place, the decision
+ *   accept = lp > -inf && (lc == -inf || log(u) < beta * (lp - lc))
+ * (the difference rounds first, then the product) - the BAD rule, the Philox blocks of the accept uniforms, the proposal, Xrec, the
+ * counts, row ownership, row0 and alignment are those above.  logw_cur, logw_prop and logw_out hold UNTEMPERED log-weights: an
+ * accepted row's logw_out has the bits of logw_prop, which the next stage of a tempered run reweights.  ttm_mh_step is this call
+ * with beta = 1 (1.0 * x is exact: the same bits), the same kernel k_mh_step.
+ * TTM_E_ARG: as ttm_mh_step, and beta NaN, <= 0 or > 1.                                                                  */
+int ttm_mh_step_tempered(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out,
+                         const double* Zprop, int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop,
+                         double* Znext, int64_t ldzn, double rho, double beta, double* Xrec, int64_t ldxr, int32_t* n_acc,
+                         int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
+                         uint32_t draw_propose, int64_t row0, void* stream);
 
 /* ---- optimisers -----------------------------------------------------------------------------------------
  * TM:3108-3114 (scipy.optimize.minimize, method 'L-BFGS-B': maxcor 10, ftol 2.22e-9, gtol 1e-5, maxls 20) as a host

@@ -112,6 +112,9 @@ _SIGNATURES = {
     'ttm_resample': (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, ctypes.c_uint64, ctypes.c_uint32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp]),
     'ttm_mh_step': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_dbl, c_vp, c_i64, c_vp, c_vp,
                                    c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_i64, c_vp]),
+    'ttm_mh_step_tempered': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_vp, c_i64,
+                                            c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_i64, c_vp]),
+    'ttm_temper_scan': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     'ttm_signal': (ctypes.c_int, [c_vp, c_dbl, c_vp]),
     'ttm_lbfgsb_minimize': (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     'ttm_optimize_separable': (ctypes.c_int, [c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_dbl, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -3216,6 +3216,75 @@ __global__ __launch_bounds__(256) void k_mh_step(const MhStep a) {
     mh_step_pair(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int)blockIdx.y, (int)gridDim.y);
 }
 
+// The weight summaries of C tempered copies of logw (ttm_temper_scan; csrc/ttm_smc.h).  One workgroup per tile of RS_TILE rows
+// with the row-pair ownership of k_weight_sums: the four rows are loaded once, then every candidate c forms q of
+// v = fl(delta_c x) against the tempered maximum fl(delta_c m) (temper_q: the product is never contracted into the subtraction
+// that follows it) and the lanes' butterflies of rs_block_sum.  The wave sums of all candidates are parked in LDS and added
+// behind ONE barrier - (w0 + w1) + (w2 + w3), the tree of rs_block_sum - by thread c, which writes the tile's integer sum and
+// its part of S2 for candidate c.  base: the maximum and the bad count of logw as k_weight_max_finish left them.
+__global__ __launch_bounds__(RS_THREADS) void k_temper_sums(const double* __restrict__ logw, int64_t N, const ttm_weight_summary* __restrict__ base, int K,
+                                                            const TemperDeltas dl, int C, int64_t ntiles, uint64_t* __restrict__ tsum,
+                                                            double* __restrict__ ts2) {
+    __shared__ uint64_t s_u[TS_CMAX][4];
+    __shared__ double s_d[TS_CMAX][4];
+    const int t = (int)threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * RS_TILE + 2 * t, r1 = r0 + RS_TILE / 2;
+    const double m = base->m;
+    double x[4];
+    rs_load2(logw, N, r0, x[0], x[1]);
+    rs_load2(logw, N, r1, x[2], x[3]);
+    for (int c = 0; c < C; ++c) {
+        const double d = dl.d[c], mc = temper_mul(d, m);
+        uint64_t q[4];
+        for (int i = 0; i < 4; ++i) q[i] = temper_q(d, x[i], mc, K);
+        uint64_t u = q[0] + q[1] + q[2] + q[3];
+        double v = (weight_sq(q[0], K) + weight_sq(q[1], K)) + (weight_sq(q[2], K) + weight_sq(q[3], K));
+        for (int s = 32; s >= 1; s >>= 1) {
+            u += (uint64_t)__shfl_xor((unsigned long long)u, s);
+            v += __shfl_xor(v, s);
+        }
+        if ((t & 63) == 0) {
+            s_u[c][t >> 6] = u;
+            s_d[c][t >> 6] = v;
+        }
+    }
+    __syncthreads();
+    if (t < C) {
+        tsum[(int64_t)t * ntiles + blockIdx.x] = s_u[t][0] + s_u[t][1] + s_u[t][2] + s_u[t][3];
+        ts2[(int64_t)t * ntiles + blockIdx.x] = (s_d[t][0] + s_d[t][1]) + (s_d[t][2] + s_d[t][3]);
+    }
+}
+static_assert(TS_CMAX <= RS_THREADS, "one thread per candidate writes the tile's sums");
+
+// one workgroup per candidate: the pass structure of k_weight_tiles without the offsets - every thread adds one tile's part of
+// S2 per pass of RS_PASS tiles, then the 256 running sums are added; T is an integer sum, whose order does not matter
+__global__ __launch_bounds__(RS_THREADS) void k_temper_finish(const uint64_t* __restrict__ tsum, const double* __restrict__ ts2, int64_t ntiles,
+                                                              const ttm_weight_summary* __restrict__ base, const TemperDeltas dl,
+                                                              ttm_weight_summary* __restrict__ summaries) {
+    __shared__ uint64_t s_w[4];
+    __shared__ double s_d[4];
+    const int t = (int)threadIdx.x, c = (int)blockIdx.x;
+    const uint64_t* ts = tsum + (int64_t)c * ntiles;
+    const double* t2 = ts2 + (int64_t)c * ntiles;
+    uint64_t part = 0;
+    double acc = 0.0;
+    for (int64_t p0 = 0; p0 < ntiles; p0 += RS_PASS) {
+        const int64_t i = p0 + t;
+        if (i < ntiles) {
+            part += ts[i];
+            acc += t2[i];
+        }
+    }
+    const uint64_t T = rs_block_sum(part, s_w);
+    const double s2 = rs_block_sum(acc, s_d);
+    if (t == 0) {
+        summaries[c].m = temper_mul(dl.d[c], base->m);
+        summaries[c].T = T;
+        summaries[c].S2 = s2;
+        summaries[c].bad = base->bad;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host side: launch planning
 // ---------------------------------------------------------------------------
@@ -4696,12 +4765,45 @@ int ttm_resample(const uint64_t* cum, int64_t N, int64_t M, int32_t scheme, uint
     return check_launch("k_resample");
 }
 
+int ttm_temper_scan(const double* logw, int64_t N, const double* delta, int32_t C, ttm_weight_summary* summaries, void* work, void* stream) {
+    if (!temper_scan_args_ok(logw, N, delta, C, summaries, work)) return set_err(TTM_E_ARG, "ttm_temper_scan: bad arguments%s");
+    const int64_t ntiles = (N + RS_TILE - 1) / RS_TILE;                      // <= 2^20
+    // the workspace: TTM_TEMPER_SCAN_WORK_WORDS(N, C) = 4 + (2 + 2 C) ntiles words - the summary of logw itself (maximum, bad count),
+    // tile maxima, bad counts, and per candidate the tile sums and the parts of S2; every word that is read was written by an
+    // earlier launch of this call
+    ttm_weight_summary* base = (ttm_weight_summary*)work;
+    double* pmax = (double*)work + 4;
+    uint64_t* pbad = (uint64_t*)work + 4 + ntiles;
+    uint64_t* tsum = (uint64_t*)work + 4 + 2 * ntiles;
+    double* ts2 = (double*)work + 4 + (2 + (int64_t)C) * ntiles;
+    TemperDeltas dl;
+    for (int c = 0; c < TS_CMAX; ++c) dl.d[c] = c < C ? delta[c] : 0.0;
+    const int K = weight_bits(N);
+    const dim3 grid((unsigned)ntiles), block(RS_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_weight_max, grid, block, 0, s, logw, N, pmax, pbad);
+    hipLaunchKernelGGL(k_weight_max_finish, dim3(1), block, 0, s, (const double*)pmax, (const uint64_t*)pbad, ntiles, base);
+    hipLaunchKernelGGL(k_temper_sums, grid, block, 0, s, logw, N, (const ttm_weight_summary*)base, K, dl, (int)C, ntiles, tsum, ts2);
+    hipLaunchKernelGGL(k_temper_finish, dim3((unsigned)C), block, 0, s, (const uint64_t*)tsum, (const double*)ts2, ntiles, (const ttm_weight_summary*)base, dl,
+                       summaries);
+    return check_launch("k_temper_finish");
+}
+
 int ttm_mh_step(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out, const double* Zprop, int64_t ldzp,
                 const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double* Xrec, int64_t ldxr,
                 int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept, uint32_t draw_propose,
                 int64_t row0, void* stream) {
-    const MhStep a = mh_step_pack(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, Xrec, ldxr, n_acc,
-                                  n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0);
+    // the step at beta = 1: 1.0 * (lp - lc) is exact, so the decision keeps its bits
+    return ttm_mh_step_tempered(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, 1.0, Xrec, ldxr, n_acc,
+                                n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0, stream);
+}
+
+int ttm_mh_step_tempered(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out, const double* Zprop,
+                         int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double beta,
+                         double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed,
+                         uint32_t draw_accept, uint32_t draw_propose, int64_t row0, void* stream) {
+    const MhStep a = mh_step_pack(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, beta, Xrec, ldxr,
+                                  n_acc, n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0);
     if (!mh_step_args_ok(a)) return set_err(TTM_E_ARG, "ttm_mh_step: bad arguments%s");
     const int64_t gx = (normal_fill_pairs(N, row0) + 255) / 256;
     if (gx > 0x7fffffff) return set_err(TTM_E_LIMIT, "ttm_mh_step: %s%lld rows are more than one launch covers", "", (long long)N);

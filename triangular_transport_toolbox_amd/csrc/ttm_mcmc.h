@@ -1,11 +1,14 @@
-// ttm_mcmc.h - one step of Metropolis-Hastings in the reference space of a fitted map (ttm_mh_step of include/ttm.h; DESIGN.md
-// section 4): the per-pair routines the kernel k_mh_step of csrc/ttm_kernels.hip and the host definition of the entry point
+// ttm_mcmc.h - one step of Metropolis-Hastings in the reference space of a fitted map (ttm_mh_step and ttm_mh_step_tempered of
+// include/ttm.h): the per-pair routines the kernel k_mh_step of csrc/ttm_kernels.hip and the host definition of the entry point
 // share.  Included at the end of csrc/ttm_rng.h (philox4x32_10, normal_pair, load_pair / store_pair come from there).
 //
 // The chain of row n lives in reference space: z' = rho z + sqrt(1 - rho^2) xi is reversible with respect to N(0, I), the
 // pulled-back target is w(x(z)) phi(z) with w = p / q, so the acceptance ratio is w(x') / w(x) for every rho in (-1, 1) - the
 // independence sampler with the map as its proposal at rho = 0.  Between two launches the caller inverts the proposal and
 // evaluates the target; one launch decides the step that was proposed by the launch before it and proposes the next one.
+// The tempered target of sequential Monte Carlo, q^(1 - beta) p^beta = q w^beta, pulls back to w(x(z))^beta phi(z): the same
+// proposal, the acceptance ratio (w(x') / w(x))^beta.  The log-weights a step reads and writes stay UNTEMPERED - beta enters the
+// comparison alone -, and ttm_mh_step is the step at beta = 1 (1.0 * x is exact: the same decision, bit for bit).
 #pragma once
 
 #include <math.h>
@@ -13,7 +16,8 @@
 
 namespace ttm {
 
-// the arguments of ttm_mh_step as the kernel takes them (s = sqrt((1 - rho)(1 + rho)), formed once on the host)
+// the arguments of ttm_mh_step / ttm_mh_step_tempered as the kernel takes them (s = sqrt((1 - rho)(1 + rho)), formed once on the
+// host; beta = 1 for ttm_mh_step)
 struct MhStep {
     double* Zcur; int64_t ldzc;
     double* Xcur; int64_t ldxc;
@@ -22,7 +26,7 @@ struct MhStep {
     const double* Xprop; int64_t ldxp;
     const double* logw_prop;
     double* Znext; int64_t ldzn;
-    double rho, s;
+    double rho, s, beta;
     double* Xrec; int64_t ldxr;
     int32_t* n_acc; int32_t* n_bad;
     int64_t N; int32_t ncols, col0;
@@ -45,10 +49,11 @@ enum { MH_REJECT = 0, MH_ACCEPT = 1, MH_BAD = 2 };
 
 // the decision of one row from the log-weight of its proposal lp, that of its current state lc and its uniform u: a proposal
 // whose weight is NaN or +inf is `bad` and rejected; one of weight zero (-inf) is rejected; a chain whose own weight is zero
-// takes the first admissible proposal
-TTM_HD int mh_decide(double lp, double lc, double u) {
+// takes the first admissible proposal.  beta: the exponent on the weight ratio (the difference is formed first and rounds once,
+// then the product: nothing here is an a * b + c that could contract)
+TTM_HD int mh_decide(double lp, double lc, double u, double beta) {
     if (lp != lp || lp == INFINITY) return MH_BAD;
-    return (lp > -INFINITY && (lc == -INFINITY || log(u) < lp - lc)) ? MH_ACCEPT : MH_REJECT;
+    return (lp > -INFINITY && (lc == -INFINITY || log(u) < beta * (lp - lc))) ? MH_ACCEPT : MH_REJECT;
 }
 
 // The rows n0 (if v0) and n0 + 1 (if v1) of a column: ONE 16-byte access when both are wanted and the address allows it,
@@ -89,7 +94,7 @@ TTM_HD void mh_step_pair(const MhStep& a, int64_t i, int j0, int jstep) {
         mh_uniform_pair(a.seed, a.draw_accept, p, u0, u1);
         mh_load2(a.logw_prop, n0, v0, v1, lp0, lp1);
         mh_load2(a.logw_cur, n0, v0, v1, lc0, lc1);
-        const int d0 = v0 ? mh_decide(lp0, lc0, u0) : MH_REJECT, d1 = v1 ? mh_decide(lp1, lc1, u1) : MH_REJECT;
+        const int d0 = v0 ? mh_decide(lp0, lc0, u0, a.beta) : MH_REJECT, d1 = v1 ? mh_decide(lp1, lc1, u1, a.beta) : MH_REJECT;
         acc0 = d0 == MH_ACCEPT;
         acc1 = d1 == MH_ACCEPT;
         if (j0 == 0) {
@@ -146,7 +151,7 @@ TTM_HD bool mh_ranges_overlap(const double* x, const double* y, int64_t N) {
     return x0 < y0 + len && y0 < x0 + len;
 }
 
-// argument check of ttm_mh_step, shared by the library and the host definition below
+// argument check of ttm_mh_step / ttm_mh_step_tempered, shared by the library and the host definition below
 TTM_HD bool mh_step_args_ok(const MhStep& a) {
     if (!a.Zcur || !a.Xcur || !a.logw_cur || a.N < 1 || a.ncols < 1 || a.col0 < 0 || a.row0 < 0 || a.N > INT64_MAX - a.row0) return false;
     if (a.draw_accept >= 0x80000000u || a.draw_propose >= 0x80000000u) return false;
@@ -154,18 +159,19 @@ TTM_HD bool mh_step_args_ok(const MhStep& a) {
     if (a.ldzc < a.N || a.ldxc < a.N || a.ldzp < a.N || a.ldxp < a.N || a.ldzn < a.N || a.ldxr < a.N) return false;   // (of matrices not in use too)
     if (a.logw_prop && (!a.Zprop || !a.Xprop || !a.logw_out)) return false;
     if (!(fabs(a.rho) < 1.0)) return false;                                      // (NaN fails the comparison)
+    if (!(a.beta > 0.0 && a.beta <= 1.0)) return false;                          // (likewise)
     if (a.logw_out && (mh_ranges_overlap(a.logw_out, a.logw_cur, a.N) || (a.logw_prop && mh_ranges_overlap(a.logw_out, a.logw_prop, a.N)))) return false;
     return true;
 }
 
 TTM_HD MhStep mh_step_pack(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out, const double* Zprop,
-                           int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double* Xrec,
-                           int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
+                           int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double beta,
+                           double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
                            uint32_t draw_propose, int64_t row0) {
     MhStep a;
     a.Zcur = Zcur; a.ldzc = ldzc; a.Xcur = Xcur; a.ldxc = ldxc; a.logw_cur = logw_cur; a.logw_out = logw_out;
     a.Zprop = Zprop; a.ldzp = ldzp; a.Xprop = Xprop; a.ldxp = ldxp; a.logw_prop = logw_prop;
-    a.Znext = Znext; a.ldzn = ldzn; a.rho = rho; a.s = sqrt((1.0 - rho) * (1.0 + rho));
+    a.Znext = Znext; a.ldzn = ldzn; a.rho = rho; a.s = sqrt((1.0 - rho) * (1.0 + rho)); a.beta = beta;
     a.Xrec = Xrec; a.ldxr = ldxr; a.n_acc = n_acc; a.n_bad = n_bad;
     a.N = N; a.ncols = ncols; a.col0 = col0; a.seed = seed; a.draw_accept = draw_accept; a.draw_propose = draw_propose; a.row0 = row0;
     return a;
@@ -174,19 +180,30 @@ TTM_HD MhStep mh_step_pack(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldx
 }  // namespace ttm
 
 #if !defined(__HIPCC__)
-// HOST BUILDS ONLY (as ttm_normal_fill in csrc/ttm_rng.h): the entry point ttm_mh_step of include/ttm.h for the host test double
-// of the C ABI - the kernel's thread body, pair after pair.
+// HOST BUILDS ONLY (as ttm_normal_fill in csrc/ttm_rng.h): the entry points ttm_mh_step_tempered and ttm_mh_step (= beta 1) of
+// include/ttm.h for the host test double of the C ABI - the kernel's thread body, pair after pair.
+extern "C" __attribute__((used, visibility("default"))) inline int ttm_mh_step_tempered(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc,
+                                                                                        const double* logw_cur, double* logw_out, const double* Zprop,
+                                                                                        int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop,
+                                                                                        double* Znext, int64_t ldzn, double rho, double beta, double* Xrec,
+                                                                                        int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols,
+                                                                                        int32_t col0, uint64_t seed, uint32_t draw_accept, uint32_t draw_propose,
+                                                                                        int64_t row0, void*) {
+    const ttm::MhStep a = ttm::mh_step_pack(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, beta, Xrec,
+                                            ldxr, n_acc, n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0);
+    if (!ttm::mh_step_args_ok(a)) return TTM_E_ARG;
+    const int64_t np = ttm::normal_fill_pairs(N, row0);
+    for (int64_t i = 0; i < np; ++i) ttm::mh_step_pair(a, i, 0, 1);
+    return TTM_OK;
+}
+
 extern "C" __attribute__((used, visibility("default"))) inline int ttm_mh_step(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur,
                                                                                double* logw_out, const double* Zprop, int64_t ldzp, const double* Xprop,
                                                                                int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho,
                                                                                double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N,
                                                                                int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
                                                                                uint32_t draw_propose, int64_t row0, void*) {
-    const ttm::MhStep a = ttm::mh_step_pack(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, Xrec, ldxr,
-                                            n_acc, n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0);
-    if (!ttm::mh_step_args_ok(a)) return TTM_E_ARG;
-    const int64_t np = ttm::normal_fill_pairs(N, row0);
-    for (int64_t i = 0; i < np; ++i) ttm::mh_step_pair(a, i, 0, 1);
-    return TTM_OK;
+    return ttm_mh_step_tempered(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, 1.0, Xrec, ldxr, n_acc,
+                                n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0, nullptr);
 }
 #endif

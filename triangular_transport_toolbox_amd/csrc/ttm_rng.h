@@ -259,3 +259,6 @@ extern "C" __attribute__((used, visibility("default"))) inline int ttm_sobol_nor
 
 // Metropolis-Hastings in the reference space of a fitted map: the accept uniforms and the routines of ttm_mh_step
 #include "ttm_mcmc.h"
+
+// sequential Monte Carlo with adaptive tempering: the routines of ttm_temper_scan (its step is ttm_mh_step_tempered of ttm_mcmc.h)
+#include "ttm_smc.h"

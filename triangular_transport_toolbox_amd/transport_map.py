@@ -1982,6 +1982,227 @@ class transport_map():
                     logw=state['logw'].cpu().numpy(), draws=state['draws'], state=state)
         return out.cpu().numpy(), info
 
+    # ---- sequential Monte Carlo with adaptive tempering (no counterpart in the reference): the particles move from the map's density
+    # q to the target p through q^(1 - beta) p^beta; the temperature search is one pass for all candidates (ttm_temper_scan), the
+    # rejuvenation the tempered step (ttm_mh_step_tempered, k_mh_step) - include/ttm.h, DESIGN.md section 4 ---------------------------
+
+    def temper_device(self, logw, N, deltas):
+        """The weight summaries of the C tempered copies deltas[c] * logw of the N log-weights `logw` (a contiguous device
+        vector of doubles) in one pass (ttm_temper_scan): a (C, 4) device tensor of doubles whose row c holds the four words
+        weights_device(deltas[c] * logw).words would hold - bit for bit - without the C x N products, cum or q.  1 <= C <= 64,
+        every delta positive and finite.  Nothing is read back here; weights.temper_ess turns the rows into effective sample
+        sizes."""
+        torch = _torch()
+        N = int(N)
+        if not 1 <= N <= weights.MAX_ROWS:
+            raise ValueError('N must be in [1, 2^30]')
+        if logw.dtype != torch.float64 or logw.dim() != 1 or logw.numel() < N or not logw.is_contiguous():
+            raise ValueError('logw must be a contiguous vector of at least N doubles')
+        d = np.ascontiguousarray(deltas, dtype=np.float64).reshape(-1)
+        C = int(d.shape[0])
+        if not 1 <= C <= weights.TEMPER_MAX or not np.all(np.isfinite(d) & (d > 0.0)):
+            raise ValueError('deltas must be 1 to %d positive finite numbers' % weights.TEMPER_MAX)
+        words = self._empty(C, 4)
+        work = self._empty(weights.temper_work_words(N, C))
+        _capi.check(self._lib.ttm_temper_scan(self._ptr(logw), N, ctypes.c_void_p(d.ctypes.data), C, self._ptr(words), self._ptr(work), self._stream()))
+        return words
+
+    def smc_device(self, log_target_pdf, particles, Xs=None, ess_target=0.5, moves=2, rho=0.5, max_stages=100, scheme='systematic', seed=0,
+                   draw=None, k0=0):
+        """Sequential Monte Carlo with adaptive tempering from the fitted map to the density exp(log_target_pdf), device-resident.
+        With S the map of the components k0 .. D - 1 given the columns in front, q the density of the map's draws and w = p / q,
+        the particles (one per row) move through the targets pi_beta = q^(1 - beta) p^beta = q w^beta, beta from 0 to 1.  Pulled
+        back to the reference space pi_beta is phi(z) w(x(z))^beta, so the proposal of mcmc_device,
+            z' = rho z + sqrt(1 - rho^2) xi,   xi ~ N(0, I),   x' = S^-1(z'),
+        which is reversible with respect to N(0, I), has the acceptance ratio (w(x') / w(x))^beta for every rho in (-1, 1).
+        Initial particles: sample_device(particles, seed, draw0, logq=...) bit for bit, logw = log p - log q (UNTEMPERED, and kept
+        so throughout), beta_0 = 0, log Z = 0.  Stage s = 1, 2, ...:
+          1. delta = weights.temper_search on the current logw with target ess_target * particles: the largest step of the
+             exponent, to 1 / 262144 of what is left, whose reweighting exp(delta logw) keeps that effective sample size (three
+             ttm_temper_scan of 64 candidates, three small read-backs);
+          2. beta_s = 1.0 exactly if delta is all that is left (or the sum would not lie strictly between beta and 1), else
+             beta + delta;
+          3. W = weights_device(delta * logw) - its summary is bit for bit the one the search saw for that candidate;
+          4. log Z += W's log_mean_weight (the product of the stages' mean weights is an unbiased estimate of the evidence);
+          5. the stage's ESS is W's;
+          6. resampling by ttm_resample(scheme, seed, r_s): Z, X and logw are row blocks of ONE (2 ncols + 1, ld) matrix, so one
+             launch gathers the whole state;
+          7. `moves` tempered Metropolis-Hastings steps at beta_s and rho (ttm_mh_step_tempered; moves + 1 launches, the first
+             proposes, the last decides), with the configured inverse and its log-density (_inverse_logq) and the target between
+             two launches, exactly as mcmc_device has them;
+          8. the run ends after the stage with beta_s = 1.
+        Draw numbers: draw0 makes the initial particles; stage s takes r_s = draw0 + 1 + (s - 1)(moves + 1) for its resampling
+        thresholds and r_s + t for the innovations and the accept uniforms of its move t = 1 .. moves: 1 + stages (moves + 1)
+        draws in all.  draw None: the map's counter, advanced by that many.
+        log_target_pdf gets the raw own coordinates as a (D - k0, particles) device tensor and returns `particles` values on the
+        device; it may be unnormalised (log Z then estimates the log of its integral).  Xs: as mcmc_device - and since
+        resampling moves a particle to another row, its conditioning columns must hold the same point in every row.
+        With the table inverse (alternate_root_finding = True, the default of separable maps) x' is interpolated, so the moves
+        target the density up to the table's round-trip error (9e-5 at C5); root_finder = 'newton' with
+        alternate_root_finding = False, or an integrated-rectifier map, makes the step exact to the root tolerance.
+        Not offered: particles sharded over ranks (no row0) - the search and the resampling would need collectives.
+        Returns (state, info): state a dict of views of the state matrix (Z, X: (D - k0, ld), standardised own columns; logw:
+        (particles,)), equally weighted particles of p; info = {log_evidence, betas (stages + 1 values from 0.0 to 1.0), ess
+        (per stage), accept_rate (per stage: mean over particles and moves), n_bad (proposals whose weight was NaN or +inf,
+        rejected), stages, draws (draw0, last draw), logw (the device vector of the final untempered log-weights)}.
+        ValueError: ess_target outside (0, 1), moves < 0, |rho| >= 1, particles < 1, an unknown scheme, draws leaving [0, 2^31),
+        an initial log-weight that is NaN or +inf, no positive weight.  RuntimeError, naming the beta reached, when max_stages
+        stages end with beta < 1."""
+        torch = _torch()
+        N, moves, k0, max_stages = int(particles), int(moves), int(k0), int(max_stages)
+        rho, ess_target = float(rho), float(ess_target)
+        if N < 1 or moves < 0 or max_stages < 1:
+            raise ValueError('particles and max_stages must be at least 1 and moves at least 0')
+        if not 0.0 < ess_target < 1.0:
+            raise ValueError('ess_target must lie in (0, 1)')
+        if not abs(rho) < 1.0:
+            raise ValueError('rho must lie in (-1, 1)')
+        if not 0 <= k0 < self.D:
+            raise ValueError('k0 must be in [0, D)')
+        sid = weights.scheme_id(scheme)
+        ncols, d = self.D - k0, self._cm.d_cols
+        c0 = d - ncols                                   # (column of component k0)
+        ld = self._ld(N)
+        seed64 = int(seed) % 2 ** 64
+        draw0 = int(draw) if draw is not None else self._draws
+        if draw0 < 0 or draw0 + 1 + moves >= 2 ** 31:
+            raise ValueError('the draws draw0 .. draw0 + 1 + stages (moves + 1) must lie in [0, 2^31)')
+        XsP = self._cols(d, N, zero=True) if Xs is None else Xs
+        if (not isinstance(XsP, torch.Tensor) or XsP.dim() != 2 or XsP.shape[0] != d or XsP.shape[1] < N or XsP.shape[1] & 1
+                or XsP.dtype != torch.float64 or XsP.device.type != self._dev.type or not XsP.is_contiguous()):
+            raise ValueError('Xs must be a contiguous (%d, even width >= %d) matrix of doubles on the device' % (d, N))
+        ldp = XsP.shape[1]
+        coef = self._pack_coeffs()
+        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
+        g_scale = None
+        if self.standardize_samples:
+            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:d]))
+        const = 0.5 * ncols * np.log(2 * np.pi)
+        st = self._stream()
+        K = weights.weight_bits(N)
+
+        def weigh(logq):
+            """log p - log q of the rows in XsP"""
+            raw = XsP[c0:d, :N]
+            if self.standardize_samples:                 # (what ttm_export computes: x * sd + mean, two roundings)
+                raw = raw * self._std_d[c0:d, None] + self._mean_d[c0:d, None]
+            logp = log_target_pdf(raw)
+            if not isinstance(logp, torch.Tensor) or logp.numel() != N:
+                raise ValueError('log_target_pdf must return a tensor of %d values' % N)
+            return (logp.reshape(N).to(device=self._dev, dtype=torch.float64) - (logq[:N] - const)).contiguous()
+
+        # the state: rows [0, ncols) Z, [ncols, 2 ncols) X, row 2 ncols logw
+        S = self._cols(2 * ncols + 1, N, zero=True)
+        logq = self._empty(N)
+        self.reference_device(N, seed=seed, draw=draw0, ncols=ncols, col0=k0, out=S[:ncols])
+        self._inverse_logq(coef, k0, self.D, S[:ncols], XsP, N, table, logq, g_scale)
+        S[ncols:2 * ncols, :N].copy_(XsP[c0:d, :N])
+        S[2 * ncols, :N].copy_(weigh(logq))
+        if bool((torch.isnan(S[2 * ncols, :N]) | (S[2 * ncols, :N] == float('inf'))).any().item()):
+            raise ValueError('an initial log-weight is NaN or +inf')
+        Zp = (self._cols(ncols, N), self._cols(ncols, N))
+        spare = self._empty(N)
+        n_acc, n_bad = self._zeros(N, dtype=torch.int32), self._zeros(N, dtype=torch.int32)
+        beta, log_z, stages = 0.0, 0.0, 0
+        betas, ess, acc = [0.0], [], []
+
+        def finish():
+            if draw is None:
+                self._draws = max(self._draws, draw0 + 1 + stages * (moves + 1))
+
+        while beta < 1.0:
+            if stages == max_stages:
+                finish()
+                raise RuntimeError('sample_smc: %d stages reached beta = %.17g, not 1: raise max_stages or lower ess_target' % (stages, beta))
+            r = draw0 + 1 + stages * (moves + 1)
+            if r + moves >= 2 ** 31:
+                finish()
+                raise ValueError('the draws draw0 .. draw0 + 1 + stages (moves + 1) must lie in [0, 2^31)')
+            logw = S[2 * ncols, :N]
+            span = 1.0 - beta
+            delta = weights.temper_search(lambda ds: weights.temper_ess(self.temper_device(logw, N, ds).cpu().numpy(), N, K), span, ess_target * N)
+            nxt = beta + delta
+            if delta == span or not beta < nxt < 1.0:
+                delta, nxt = span, 1.0
+            W = self.weights_device((delta * logw).contiguous(), N)
+            try:
+                summ = W.importance_summary()
+            except ValueError:
+                finish()
+                raise
+            log_z += summ['log_mean_weight']
+            ess.append(summ['ess'])
+            S = self.resample_device(S, N, W, scheme=scheme, seed=seed, draw=r, check=False)
+            beta = nxt
+            betas.append(beta)
+            stages += 1
+            Zcur, Xcur = S[:ncols], S[ncols:2 * ncols]
+            lw = [S[2 * ncols], spare]
+            lwp = None
+            n_acc.zero_()
+            for t in range(moves + 1 if moves else 0):
+                accept, propose = t >= 1, t < moves
+                zn = Zp[t & 1] if propose else None
+                _capi.check(self._lib.ttm_mh_step_tempered(
+                    self._ptr(Zcur), ld, self._ptr(Xcur), ld, self._ptr(lw[0]), self._ptr(lw[1]) if accept else None,
+                    self._ptr(Zp[(t - 1) & 1]) if accept else None, ld, self._ptr(XsP, c0 * ldp) if accept else None, ldp,
+                    self._ptr(lwp) if accept else None, self._ptr(zn), ld, rho, beta, None, ld, self._ptr(n_acc), self._ptr(n_bad), N, ncols, k0,
+                    seed64, r + t if accept else 0, r + t + 1 if propose else 0, 0, st))
+                if accept:
+                    lw.reverse()
+                if propose:
+                    self._inverse_logq(coef, k0, self.D, zn, XsP, N, table, logq, g_scale)
+                    lwp = weigh(logq)
+            if lw[0] is spare:                           # (an odd number of moves leaves the log-weights in the spare vector)
+                S[2 * ncols, :N].copy_(spare)
+            acc.append(n_acc.sum() if moves else None)
+        finish()
+        rates = [float(a.item()) / (N * moves) if a is not None else 0.0 for a in acc]
+        state = dict(Z=S[:ncols], X=S[ncols:2 * ncols], logw=S[2 * ncols, :N])
+        info = dict(log_evidence=log_z, betas=betas, ess=ess, accept_rate=rates, n_bad=int(n_bad.sum().item()), stages=stages,
+                    draws=(draw0, draw0 + stages * (moves + 1)), logw=state['logw'])
+        return state, info
+
+    def sample_smc(self, log_target_pdf, N, X_star=None, ess_target=0.5, moves=2, rho=0.5, max_stages=100, scheme='systematic', seed=0, draw=None,
+                   target_on_device=False):
+        """Tempered sequential Monte Carlo from the fitted map (smc_device, which states the algorithm and the draw numbers): N
+        equally weighted particles of the density exp(log_target_pdf) / Z and an unbiased estimate of the evidence Z - between
+        importance resampling (sample_importance), which loses its effective sample size to a mediocre fit, and the chains of
+        sample_mcmc, which give no evidence.  Returns (X, info): X an N x (D - k0) array of raw coordinates (k0: the first
+        inverted component); info as smc_device - 'log_evidence', 'betas' (the tempering path: few stages mean a fit close to
+        the target), 'ess', 'accept_rate', 'n_bad', 'stages', 'draws' -, 'logw' as an (N,) array.
+        X_star: no conditioning or ONE conditioning point of shape (E,) / (1, E) for all particles (resampling moves particles
+        between rows, so a point per row has no meaning here).  log_target_pdf gets the raw own coordinates as an N x (D - k0)
+        NumPy array and returns N values (the convention of sample_mcmc; it may be unnormalised); target_on_device True: a
+        (D - k0, N) device tensor in, a device tensor out - then nothing but the final particles and a few summary words per
+        stage cross PCIe.  The initial particles are sample(N, X_star, seed, draw0, logdensity=True), bit for bit.
+        ValueError and RuntimeError: as smc_device, and a target that does not return N values.
+        With the table inverse the moves target the density up to the table's round-trip error; see smc_device."""
+        N = int(N)
+        if N < 1:
+            raise ValueError('N must be at least 1')
+        k0, E, Xstar_cols = self._conditioning(X_star)
+        if Xstar_cols is not None and not (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1):
+            raise ValueError('X_star must be one conditioning point for all particles')
+        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=Xstar_cols is not None)
+        ncols = self.D - k0
+        target = log_target_pdf
+        if not target_on_device:
+            def target(raw):
+                logp = np.asarray(log_target_pdf(np.ascontiguousarray(raw.cpu().numpy().T)), dtype=float).reshape(-1)
+                if logp.shape[0] != N:
+                    raise ValueError('log_target_pdf must return %d values' % N)
+                return self._to_dev(logp)
+        state, info = self.smc_device(target, N, Xs=Xs, ess_target=ess_target, moves=moves, rho=rho, max_stages=max_stages, scheme=scheme, seed=seed,
+                                      draw=draw, k0=k0)
+        c0 = self._cm.d_cols - ncols
+        out = self._empty(N, ncols)
+        mean = self._ptr(self._mean_d, c0) if self.standardize_samples else None
+        sd = self._ptr(self._std_d, c0) if self.standardize_samples else None
+        _capi.check(self._lib.ttm_export(self._ptr(state['X']), state['X'].shape[1], N, 0, ncols, mean, sd, self._ptr(out), self._stream()))
+        info = dict(info, logw=info['logw'].cpu().numpy())
+        return out.cpu().numpy(), info
+
     def _inverse_table(self, coef, k0, k1, Zs, Xs, N, resolution=1001, start_distance=10, row0=0):
         """TM:3987-4084 for all components: tabulate, index and look up on the device.  interp1d sorts its
         abscissae (stable) first; monotone tables are already sorted, which the index kernel verifies -
