@@ -38,6 +38,7 @@ import os
 import numpy as np
 
 from . import _capi, comm, lbfgsb, qmc, quantile, termtable, weights
+from .proposal import Proposal
 
 __all__ = ['transport_map']
 
@@ -272,6 +273,12 @@ class transport_map():
     def _cols(self, ncols, N, zero=False):
         """Column-major ncols x N device matrix with padded leading dimension (a (ncols, ld) tensor)."""
         return (self._zeros if zero else self._empty)(int(ncols), self._ld(N))
+
+    def _inv_std(self, a, b):
+        """1 / X_std of the columns [a, b) on the device - the g_scale of a density in raw coordinates; None: unstandardised samples."""
+        if not self.standardize_samples:
+            return None
+        return self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[a:b]))
 
     def _stream(self):
         if self._dev.type != 'cuda':
@@ -1073,11 +1080,16 @@ class transport_map():
             ok = False
         return ok
 
+    @property
+    def _table_inverse(self):
+        """The table inverse is the configured one (separable maps with alternate_root_finding); otherwise a root search."""
+        return self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
+
     def _eager_tables(self):
         # the default inverse tables ride along with the fold of a new coefficient vector (their flags come back behind the same
         # synchronisation) - once this map HAS been inverted by table: a caller that only runs forward / density passes over
         # many coefficient vectors pays neither the launch nor the allocations
-        return (self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity' and self._cm.u_enabled and
+        return (self._table_inverse and self._cm.u_enabled and
                 getattr(self, '_cm', None) is not None and self._cm.u_h_cls > 0 and getattr(self, '_inverse_seen', False))
 
     def _launch_default_tables(self, coef, resolution=1001, start_distance=10, h_unsorted=None, staged=None):
@@ -1221,7 +1233,7 @@ class transport_map():
         skip = self._cm.d_cols - self.D
         if skip > 0:
             Xr[:skip, :N].copy_(Xs[:skip, :N])
-        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity' and self.root_search_truncation
+        table = self._table_inverse and self.root_search_truncation
         rc = _capi.TTM_E_UNSUPPORTED
         if table and self._dev.type == 'cuda':
             resolution, start_distance, nb = 1001, 10, self._inv_nb()
@@ -1248,7 +1260,7 @@ class transport_map():
         coef = self._current(coef)
         X = self._cols(self._cm.d_cols, N, zero=True) if X is None else X
         if table is None:
-            table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
+            table = self._table_inverse
         if logq is not None and logq is not False:
             logq = self._empty(N) if logq is True else logq
             self._inverse_logq(coef, 0, self.D, Zs, X, N, table, logq, g_scale)
@@ -1373,7 +1385,7 @@ class transport_map():
         E, D = self._cm.d_cols - self.D, self.D
         std = np.asarray(self.X_std, dtype=float)[E:E + D]
         mean = np.asarray(self.X_mean, dtype=float)[E:E + D]
-        g_scale = self._to_dev(np.ascontiguousarray(1.0 / std))
+        g_scale = self._inv_std(E, E + D)
         ld_affine = self._to_dev(np.ascontiguousarray(np.column_stack((std, mean))))
         G = self.score_device(Xs, N, coef, g_scale=g_scale, ld_affine=ld_affine)
         return self._export(G, N, 0, D, False)
@@ -1413,9 +1425,7 @@ class transport_map():
             raise ValueError('X must have shape (N, %d)' % self._cm.d_cols)
         N = X.shape[0]
         E, D = self._cm.d_cols - self.D, self.D
-        g_scale = None
-        if self.standardize_samples:
-            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[E:E + D]))
+        g_scale = self._inv_std(E, E + D)
         Xs = self._import(X, bool(self.standardize_samples))
         coef = self._pack_coeffs()
         logp, G = self.logdensity_device(Xs, N, coef, logp=self._empty(N), G=self._cols(D, N) if score else None, g_scale=g_scale)
@@ -1550,7 +1560,6 @@ class transport_map():
         logq = logdet - sumsq / 2.  That is the change-of-variables density of the draws with every component evaluated on
         the standardised sample - NOT the convention of evaluate_pullback_density, which follows the reference in taking the
         log-determinant's derivative basis on the raw sample."""
-        torch = _torch()
         if self.monotonicity.lower() != 'separable monotonicity':
             self._inverse_bisect(coef, k0, k1, Zs, Xs, N, logq=logq, g_scale=g_scale)
             return
@@ -1558,10 +1567,15 @@ class transport_map():
             self._inverse_table(coef, k0, k1, Zs, Xs, N)
         else:
             self._inverse_bisect(coef, k0, k1, Zs, Xs, N)
+        self._density_pass(coef, k0, k1, Xs, N, g_scale, logq)
+
+    def _density_pass(self, coef, k0, k1, Xs, N, g_scale, logq, Z=None):
+        """logq[:N] = logdet - sumsq / 2 of the components k0 .. k1 - 1 at the rows of the standardised (d, width) matrix Xs: one
+        ttm_forward with sigma = 1 / g_scale (the terms of _inverse_logq).  Z (k1 - k0, its own width): receives z = S(x) too."""
         logdet, sumsq = self._empty(N), self._empty(N)
-        sigma = None if g_scale is None else torch.reciprocal(g_scale)
+        sigma = None if g_scale is None else _torch().reciprocal(g_scale)
         _capi.check(self._lib.ttm_forward(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), self._ptr(Xs), Xs.shape[1], N, k0, k1,
-                                          None, N, self._ptr(logdet), self._ptr(sigma), self._ptr(sumsq), self._stream()))
+                                          self._ptr(Z), N if Z is None else Z.shape[1], self._ptr(logdet), self._ptr(sigma), self._ptr(sumsq), self._stream()))
         logq[:N].copy_(logdet - 0.5 * sumsq)
 
     # ---- sampling: reference draws made where the inverse reads them (no counterpart in the reference: its callers draw Z with
@@ -1633,35 +1647,32 @@ class transport_map():
         N = int(N)
         if N < 1:
             raise ValueError('N must be at least 1')
-        k0, E, Xstar_cols = self._conditioning(X_star)
-        coef = self._pack_coeffs()
-        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
-        one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
-        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
-        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=self.D - k0, col0=k0, row0=row0, sequence=sequence, scramble=scramble)
+        P = Proposal.from_star(self, N, X_star, density=logdensity)
+        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=P.ncols, col0=P.k0, row0=row0, sequence=sequence, scramble=scramble)
         if not logdensity:
-            return self._inverse_export(coef, k0, self.D, Zs, Xs, N, table)
-        g_scale = None
-        if self.standardize_samples:
-            c0 = self._cm.d_cols - self.D + k0          # (column of component k0)
-            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:c0 + self.D - k0]))
+            return self._inverse_export(P.coef, P.k0, self.D, Zs, P.Xs, N, P.table)
         logq = self._empty(N)
-        X = self._inverse_export(coef, k0, self.D, Zs, Xs, N, table, logq=logq, g_scale=g_scale)
-        return X, logq[:N].cpu().numpy() - 0.5 * (self.D - k0) * np.log(2 * np.pi)
+        X = self._inverse_export(P.coef, P.k0, self.D, Zs, P.Xs, N, P.table, logq=logq, g_scale=P.g_scale)
+        return X, logq[:N].cpu().numpy() - P.const
 
     # ---- importance weights and resampling (no counterpart in the reference): logw = log p - log q of the draws becomes weights
     # in fixed point on the device (ttm_weight_scan), diagnostics of the fit as a proposal, and an equally weighted ensemble
     # (ttm_resample) - include/ttm.h, DESIGN.md section 4 ----------------------------------------------------------------------
 
+    def _check_logw(self, logw, N):
+        """N as an int, for N log-weights in the device vector `logw`."""
+        N = int(N)
+        if not 1 <= N <= weights.MAX_ROWS:
+            raise ValueError('N must be in [1, 2^30]')
+        if logw.dtype != _torch().float64 or logw.dim() != 1 or logw.numel() < N or not logw.is_contiguous():
+            raise ValueError('logw must be a contiguous vector of at least N doubles')
+        return N
+
     def weights_device(self, logw, N, q=False):
         """The fixed-point weights of the N log-weights `logw` (a device tensor of doubles): a weights.Weights with cum, the
         summary words and K, all on the device - nothing is read back here.  q True: the weights themselves are kept as well."""
         torch = _torch()
-        N = int(N)
-        if not 1 <= N <= weights.MAX_ROWS:
-            raise ValueError('N must be in [1, 2^30]')
-        if logw.dtype != torch.float64 or logw.dim() != 1 or logw.numel() < N or not logw.is_contiguous():
-            raise ValueError('logw must be a contiguous vector of at least N doubles')
+        N = self._check_logw(logw, N)
         cum = self._empty(N, dtype=torch.int64)
         qbuf = self._empty(N, dtype=torch.int64) if q else None
         words = self._empty(4)
@@ -1745,47 +1756,31 @@ class transport_map():
         draws of the same (seed, draw).  Returns (X_resampled (M x D), info): info['ess'] the effective sample size of the N
         draws, info['log_mean_weight'] the log of the mean weight (the evidence estimate), info['idx'] the ancestors - row j is
         row idx[j] of the draws -, info['logw'] the N log-weights.  ValueError when a weight is NaN or +inf or none is positive."""
-        torch = _torch()
         N = int(N)
         M = N if M is None else int(M)
         if N < 1 or M < 1:
             raise ValueError('N and M must be at least 1')
         weights.scheme_id(scheme)
         draw = self._take_draw(draw)
-        k0, E, Xstar_cols = self._conditioning(X_star)
-        coef = self._pack_coeffs()
-        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
-        one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
-        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
-        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=self.D - k0, col0=k0, sequence=sequence, scramble=scramble)
-        g_scale = None
-        if self.standardize_samples:
-            c0 = self._cm.d_cols - self.D + k0          # (column of component k0)
-            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:c0 + self.D - k0]))
+        P = Proposal.from_star(self, N, X_star)
+        Zs = self.reference_device(N, seed=seed, draw=draw, ncols=P.ncols, col0=P.k0, sequence=sequence, scramble=scramble)
         logq = self._empty(N)
-        self._inverse_logq(coef, k0, self.D, Zs, Xs, N, table, logq, g_scale)
+        P.inverse_logq(Zs, logq)
         d, skip = self._cm.d_cols, self.skip_dimensions
-        const = 0.5 * (self.D - k0) * np.log(2 * np.pi)
         if target_on_device:
-            raw = Xs[skip:d, :N]
-            if self.standardize_samples:                 # (what ttm_export computes: x * sd + mean, two roundings)
-                raw = raw * self._std_d[skip:d, None] + self._mean_d[skip:d, None]
-            logp = log_target_pdf(raw)
-            if not isinstance(logp, torch.Tensor) or logp.numel() != N:
-                raise ValueError('log_target_pdf must return a tensor of N values')
-            logw = (logp.reshape(N).to(torch.float64) - (logq[:N] - const)).contiguous()
+            logw = P.weigh(log_target_pdf, logq, first=skip)      # (every returned column, conditioning columns included)
             w = self.weights_device(logw, N)
-            Y, anc = self.resample_device(Xs, N, w, M=M, scheme=scheme, seed=seed, draw=draw, idx=True)
+            Y, anc = self.resample_device(P.Xs, N, w, M=M, scheme=scheme, seed=seed, draw=draw, idx=True)
             Xr = self._export(Y, M, 0, d, self.standardize_samples)[:, skip:]
             anc, logw = anc.cpu().numpy(), logw.cpu().numpy()
         else:
-            X = self._export(Xs, N, 0, d, self.standardize_samples)[:, skip:]
+            X = self._export(P.Xs, N, 0, d, self.standardize_samples)[:, skip:]
             logp = np.asarray(log_target_pdf(X), dtype=float).reshape(-1)
             if logp.shape[0] != N:
                 raise ValueError('log_target_pdf must return N values')
-            logw = logp - (logq[:N].cpu().numpy() - const)
+            logw = logp - (logq[:N].cpu().numpy() - P.const)
             w = self.weights_device(self._to_dev(logw), N)
-            _, anc = self.resample_device(Xs[:0], N, w, M=M, scheme=scheme, seed=seed, draw=draw, idx=True)
+            _, anc = self.resample_device(P.Xs[:0], N, w, M=M, scheme=scheme, seed=seed, draw=draw, idx=True)
             anc = anc.cpu().numpy()
             Xr = X[anc]
         info = dict(w.importance_summary(), idx=anc, logw=logw)
@@ -1835,9 +1830,7 @@ class transport_map():
         if not 0 <= k0 < self.D or row0 < 0:
             raise ValueError('k0 must be in [0, D) and row0 at least 0')
         cont = isinstance(init, dict)
-        ncols, d = self.D - k0, self._cm.d_cols
-        c0 = d - ncols                                   # (column of component k0)
-        ld = self._ld(N)
+        ncols, ld = self.D - k0, self._ld(N)
         seed64 = int(seed) % 2 ** 64
         if cont:
             for key, shape, dtype in (('Z', (ncols, ld), torch.float64), ('X', (ncols, ld), torch.float64), ('logw', (N,), torch.float64),
@@ -1865,31 +1858,10 @@ class transport_map():
             init = np.asarray(init, dtype=float)
             if init.shape != (N, ncols):
                 raise ValueError('init must be a %d x %d array or the state of an earlier run' % (N, ncols))
-        XsP = self._cols(d, N, zero=True) if Xs is None else Xs
-        if (not isinstance(XsP, torch.Tensor) or XsP.dim() != 2 or XsP.shape[0] != d or XsP.shape[1] < N or XsP.shape[1] & 1
-                or XsP.dtype != torch.float64 or XsP.device.type != self._dev.type or not XsP.is_contiguous()):
-            raise ValueError('Xs must be a contiguous (%d, even width >= %d) matrix of doubles on the device' % (d, N))
-        ldp = XsP.shape[1]                               # (any such width: the state below has its own leading dimension ld)
+        P = Proposal(self, N, k0, Xs)
+        c0, d = P.c0, P.d
         if draw is None:
             self._draws = max(self._draws, draw0 + steps + 1)
-        coef = self._pack_coeffs()
-        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
-        g_scale = None
-        if self.standardize_samples:
-            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:d]))
-        const = 0.5 * ncols * np.log(2 * np.pi)
-        st = self._stream()
-
-        def weigh(logq):
-            """log p - log q of the rows in XsP"""
-            raw = XsP[c0:d, :N]
-            if self.standardize_samples:                 # (what ttm_export computes: x * sd + mean, two roundings)
-                raw = raw * self._std_d[c0:d, None] + self._mean_d[c0:d, None]
-            logp = log_target_pdf(raw)
-            if not isinstance(logp, torch.Tensor) or logp.numel() != N:
-                raise ValueError('log_target_pdf must return a tensor of %d values' % N)
-            return (logp.reshape(N).to(device=self._dev, dtype=torch.float64) - (logq[:N] - const)).contiguous()
-
         logq = self._empty(N)
         if cont:
             Zcur, Xcur, logw = init['Z'].clone(), init['X'].clone(), init['logw'].clone()
@@ -1897,42 +1869,25 @@ class transport_map():
         else:
             if init is not None:
                 init_d = self._to_dev(init)              # (held by name: a temporary would be freed before the import reads it)
-                _capi.check(self._lib.ttm_import(self._ptr(init_d), N, ncols, self._ptr(self._mean_d, c0) if self.standardize_samples else None,
-                                                 self._ptr(self._std_d, c0) if self.standardize_samples else None, self._ptr(XsP, c0 * ldp), ldp, st))
+                mean, sd = (self._ptr(self._mean_d, c0), self._ptr(self._std_d, c0)) if self.standardize_samples else (None, None)
+                _capi.check(self._lib.ttm_import(self._ptr(init_d), N, ncols, mean, sd, self._ptr(P.Xs, c0 * P.ldp), P.ldp, self._stream()))
                 Zcur = self._cols(ncols, N)
-                logdet, sumsq = self._empty(N), self._empty(N)
-                sigma = None if g_scale is None else torch.reciprocal(g_scale)
-                _capi.check(self._lib.ttm_forward(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), self._ptr(XsP), ldp, N, k0, self.D,
-                                                  self._ptr(Zcur), ld, self._ptr(logdet), self._ptr(sigma), self._ptr(sumsq), st))
-                logq.copy_(logdet - 0.5 * sumsq)
+                self._density_pass(P.coef, k0, self.D, P.Xs, N, P.g_scale, logq, Z=Zcur)
             else:
                 Zcur = self.reference_device(N, seed=seed, draw=draw0, ncols=ncols, col0=k0, row0=row0)
-                self._inverse_logq(coef, k0, self.D, Zcur, XsP, N, table, logq, g_scale)
+                P.inverse_logq(Zcur, logq)
             Xcur = self._cols(ncols, N, zero=True)       # (its own matrix of leading dimension ld, whatever the width of Xs)
-            Xcur[:, :N].copy_(XsP[c0:d, :N])
-            logw = weigh(logq)
+            Xcur[:, :N].copy_(P.Xs[c0:d, :N])
+            logw = P.weigh(log_target_pdf, logq)
             if bool((torch.isnan(logw) | (logw == float('inf'))).any().item()):       # (the one read-back of the run)
                 raise ValueError('an initial log-weight is NaN or +inf')
             n_acc, n_bad, done = self._zeros(N, dtype=torch.int32), self._zeros(N, dtype=torch.int32), 0
         Zp = (self._cols(ncols, N), self._cols(ncols, N))
-        lw = [logw, self._empty(N)]
-        lwp = None
+        spare = self._empty(N)
         trace = self._empty(kept, ncols, ld)
-        for t in range(steps + 1):
-            accept, propose = t >= 1, t < steps
-            rec = trace[(t - burn) // thin - 1] if (accept and t > burn and (t - burn) % thin == 0) else None
-            zn = Zp[t & 1] if propose else None
-            _capi.check(self._lib.ttm_mh_step(self._ptr(Zcur), ld, self._ptr(Xcur), ld, self._ptr(lw[0]), self._ptr(lw[1]) if accept else None,
-                                              self._ptr(Zp[(t - 1) & 1]) if accept else None, ld, self._ptr(XsP, c0 * ldp) if accept else None, ldp,
-                                              self._ptr(lwp) if accept else None, self._ptr(zn), ld, rho, self._ptr(rec), ld,
-                                              self._ptr(n_acc), self._ptr(n_bad), N, ncols, k0, seed64, draw0 + t if accept else 0,
-                                              draw0 + t + 1 if propose else 0, row0, st))
-            if accept:
-                lw.reverse()
-            if propose:
-                self._inverse_logq(coef, k0, self.D, zn, XsP, N, table, logq, g_scale)
-                lwp = weigh(logq)
-        state = dict(Z=Zcur, X=Xcur, logw=lw[0], n_acc=n_acc, n_bad=n_bad, steps=done + steps, draws=(draw0, draw0 + steps),
+        logw = P.moves(log_target_pdf, steps, Zcur, Xcur, (logw, spare), Zp, n_acc, n_bad, logq, rho, 1.0, seed64, draw0, row0,
+                       record=lambda t: trace[(t - burn) // thin - 1] if (t > burn and (t - burn) % thin == 0) else None)
+        state = dict(Z=Zcur, X=Xcur, logw=logw, n_acc=n_acc, n_bad=n_bad, steps=done + steps, draws=(draw0, draw0 + steps),
                      seed=seed64, row0=row0)
         return trace, state
 
@@ -1960,24 +1915,12 @@ class transport_map():
         N = int(chains)
         if N < 1:
             raise ValueError('chains must be at least 1')
-        k0, E, Xstar_cols = self._conditioning(X_star)
-        one_point = Xstar_cols is not None and (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1)
-        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=one_point)
-        ncols = self.D - k0
-        target = log_target_pdf
-        if not target_on_device:
-            def target(raw):
-                logp = np.asarray(log_target_pdf(np.ascontiguousarray(raw.cpu().numpy().T)), dtype=float).reshape(-1)
-                if logp.shape[0] != N:
-                    raise ValueError('log_target_pdf must return %d values' % N)
-                return self._to_dev(logp)
-        trace, state = self.mcmc_device(target, N, steps, Xs=Xs, rho=rho, burn=burn, thin=thin, seed=seed, draw=draw, row0=row0, init=init, k0=k0)
-        kept, c0 = trace.shape[0], self._cm.d_cols - ncols
-        out = self._empty(kept, N, ncols)
-        mean = self._ptr(self._mean_d, c0) if self.standardize_samples else None
-        sd = self._ptr(self._std_d, c0) if self.standardize_samples else None
-        for i in range(kept):
-            _capi.check(self._lib.ttm_export(self._ptr(trace[i]), trace.shape[2], N, 0, ncols, mean, sd, self._ptr(out[i]), self._stream()))
+        P = Proposal.from_star(self, N, X_star, density=False)           # (mcmc_device makes its own, with the density's part)
+        target = log_target_pdf if target_on_device else P.host_target(log_target_pdf)
+        trace, state = self.mcmc_device(target, N, steps, Xs=P.Xs, rho=rho, burn=burn, thin=thin, seed=seed, draw=draw, row0=row0, init=init, k0=P.k0)
+        out = self._empty(trace.shape[0], N, P.ncols)
+        for i in range(trace.shape[0]):
+            P.export_own(trace[i], out[i])
         info = dict(accept_rate=state['n_acc'].cpu().numpy() / float(state['steps']), n_bad=state['n_bad'].cpu().numpy(),
                     logw=state['logw'].cpu().numpy(), draws=state['draws'], state=state)
         return out.cpu().numpy(), info
@@ -1992,12 +1935,7 @@ class transport_map():
         weights_device(deltas[c] * logw).words would hold - bit for bit - without the C x N products, cum or q.  1 <= C <= 64,
         every delta positive and finite.  Nothing is read back here; weights.temper_ess turns the rows into effective sample
         sizes."""
-        torch = _torch()
-        N = int(N)
-        if not 1 <= N <= weights.MAX_ROWS:
-            raise ValueError('N must be in [1, 2^30]')
-        if logw.dtype != torch.float64 or logw.dim() != 1 or logw.numel() < N or not logw.is_contiguous():
-            raise ValueError('logw must be a contiguous vector of at least N doubles')
+        N = self._check_logw(logw, N)
         d = np.ascontiguousarray(deltas, dtype=np.float64).reshape(-1)
         C = int(d.shape[0])
         if not 1 <= C <= weights.TEMPER_MAX or not np.all(np.isfinite(d) & (d > 0.0)):
@@ -2060,44 +1998,20 @@ class transport_map():
         if not 0 <= k0 < self.D:
             raise ValueError('k0 must be in [0, D)')
         sid = weights.scheme_id(scheme)
-        ncols, d = self.D - k0, self._cm.d_cols
-        c0 = d - ncols                                   # (column of component k0)
-        ld = self._ld(N)
+        ncols = self.D - k0
         seed64 = int(seed) % 2 ** 64
         draw0 = int(draw) if draw is not None else self._draws
         if draw0 < 0 or draw0 + 1 + moves >= 2 ** 31:
             raise ValueError('the draws draw0 .. draw0 + 1 + stages (moves + 1) must lie in [0, 2^31)')
-        XsP = self._cols(d, N, zero=True) if Xs is None else Xs
-        if (not isinstance(XsP, torch.Tensor) or XsP.dim() != 2 or XsP.shape[0] != d or XsP.shape[1] < N or XsP.shape[1] & 1
-                or XsP.dtype != torch.float64 or XsP.device.type != self._dev.type or not XsP.is_contiguous()):
-            raise ValueError('Xs must be a contiguous (%d, even width >= %d) matrix of doubles on the device' % (d, N))
-        ldp = XsP.shape[1]
-        coef = self._pack_coeffs()
-        table = self.alternate_root_finding and self.monotonicity.lower() == 'separable monotonicity'
-        g_scale = None
-        if self.standardize_samples:
-            g_scale = self._to_dev(np.ascontiguousarray(1.0 / np.asarray(self.X_std, dtype=float)[c0:d]))
-        const = 0.5 * ncols * np.log(2 * np.pi)
-        st = self._stream()
+        P = Proposal(self, N, k0, Xs)
         K = weights.weight_bits(N)
-
-        def weigh(logq):
-            """log p - log q of the rows in XsP"""
-            raw = XsP[c0:d, :N]
-            if self.standardize_samples:                 # (what ttm_export computes: x * sd + mean, two roundings)
-                raw = raw * self._std_d[c0:d, None] + self._mean_d[c0:d, None]
-            logp = log_target_pdf(raw)
-            if not isinstance(logp, torch.Tensor) or logp.numel() != N:
-                raise ValueError('log_target_pdf must return a tensor of %d values' % N)
-            return (logp.reshape(N).to(device=self._dev, dtype=torch.float64) - (logq[:N] - const)).contiguous()
-
         # the state: rows [0, ncols) Z, [ncols, 2 ncols) X, row 2 ncols logw
         S = self._cols(2 * ncols + 1, N, zero=True)
         logq = self._empty(N)
         self.reference_device(N, seed=seed, draw=draw0, ncols=ncols, col0=k0, out=S[:ncols])
-        self._inverse_logq(coef, k0, self.D, S[:ncols], XsP, N, table, logq, g_scale)
-        S[ncols:2 * ncols, :N].copy_(XsP[c0:d, :N])
-        S[2 * ncols, :N].copy_(weigh(logq))
+        P.inverse_logq(S[:ncols], logq)
+        S[ncols:2 * ncols, :N].copy_(P.Xs[P.c0:P.d, :N])
+        S[2 * ncols, :N].copy_(P.weigh(log_target_pdf, logq))
         if bool((torch.isnan(S[2 * ncols, :N]) | (S[2 * ncols, :N] == float('inf'))).any().item()):
             raise ValueError('an initial log-weight is NaN or +inf')
         Zp = (self._cols(ncols, N), self._cols(ncols, N))
@@ -2136,24 +2050,9 @@ class transport_map():
             beta = nxt
             betas.append(beta)
             stages += 1
-            Zcur, Xcur = S[:ncols], S[ncols:2 * ncols]
-            lw = [S[2 * ncols], spare]
-            lwp = None
             n_acc.zero_()
-            for t in range(moves + 1 if moves else 0):
-                accept, propose = t >= 1, t < moves
-                zn = Zp[t & 1] if propose else None
-                _capi.check(self._lib.ttm_mh_step_tempered(
-                    self._ptr(Zcur), ld, self._ptr(Xcur), ld, self._ptr(lw[0]), self._ptr(lw[1]) if accept else None,
-                    self._ptr(Zp[(t - 1) & 1]) if accept else None, ld, self._ptr(XsP, c0 * ldp) if accept else None, ldp,
-                    self._ptr(lwp) if accept else None, self._ptr(zn), ld, rho, beta, None, ld, self._ptr(n_acc), self._ptr(n_bad), N, ncols, k0,
-                    seed64, r + t if accept else 0, r + t + 1 if propose else 0, 0, st))
-                if accept:
-                    lw.reverse()
-                if propose:
-                    self._inverse_logq(coef, k0, self.D, zn, XsP, N, table, logq, g_scale)
-                    lwp = weigh(logq)
-            if lw[0] is spare:                           # (an odd number of moves leaves the log-weights in the spare vector)
+            cur = P.moves(log_target_pdf, moves, S[:ncols], S[ncols:2 * ncols], (S[2 * ncols], spare), Zp, n_acc, n_bad, logq, rho, beta, seed64, r)
+            if cur is spare:                             # (an odd number of moves leaves the log-weights in the spare vector)
                 S[2 * ncols, :N].copy_(spare)
             acc.append(n_acc.sum() if moves else None)
         finish()
@@ -2181,25 +2080,12 @@ class transport_map():
         N = int(N)
         if N < 1:
             raise ValueError('N must be at least 1')
-        k0, E, Xstar_cols = self._conditioning(X_star)
-        if Xstar_cols is not None and not (Xstar_cols.ndim == 1 or Xstar_cols.shape[0] == 1):
-            raise ValueError('X_star must be one conditioning point for all particles')
-        Xs = self._conditioned_cols(Xstar_cols, E, N, one_point=Xstar_cols is not None)
-        ncols = self.D - k0
-        target = log_target_pdf
-        if not target_on_device:
-            def target(raw):
-                logp = np.asarray(log_target_pdf(np.ascontiguousarray(raw.cpu().numpy().T)), dtype=float).reshape(-1)
-                if logp.shape[0] != N:
-                    raise ValueError('log_target_pdf must return %d values' % N)
-                return self._to_dev(logp)
-        state, info = self.smc_device(target, N, Xs=Xs, ess_target=ess_target, moves=moves, rho=rho, max_stages=max_stages, scheme=scheme, seed=seed,
-                                      draw=draw, k0=k0)
-        c0 = self._cm.d_cols - ncols
-        out = self._empty(N, ncols)
-        mean = self._ptr(self._mean_d, c0) if self.standardize_samples else None
-        sd = self._ptr(self._std_d, c0) if self.standardize_samples else None
-        _capi.check(self._lib.ttm_export(self._ptr(state['X']), state['X'].shape[1], N, 0, ncols, mean, sd, self._ptr(out), self._stream()))
+        P = Proposal.from_star(self, N, X_star, one_point_only=True, density=False)
+        target = log_target_pdf if target_on_device else P.host_target(log_target_pdf)
+        state, info = self.smc_device(target, N, Xs=P.Xs, ess_target=ess_target, moves=moves, rho=rho, max_stages=max_stages, scheme=scheme, seed=seed,
+                                      draw=draw, k0=P.k0)
+        out = self._empty(N, P.ncols)
+        P.export_own(state['X'], out)
         info = dict(info, logw=info['logw'].cpu().numpy())
         return out.cpu().numpy(), info
 
