@@ -20,40 +20,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-UC_LEN, U_TSTRIDE, U_GSTRIDE, U_GHALF, UCF_OWN, PLAN_HF = 8, 14, 24, 12, 1, 1       # include/ttm.h
-
-
 def u_section_quotient(tm, T):
-    """m''(t) / m'(t) of every component at the raw samples T (rows x D), from the U section of the current coefficient vector."""
-    cm = tm._cm
-    coef = tm._pack_coeffs()
-    fold = coef._ttm_fold.cpu().numpy()
-    U = fold[int(tm._lib.ttm_uform_offset(tm._pp)):]
-    uc = np.asarray(cm.ucomp[:cm.D * UC_LEN]).reshape(-1, UC_LEN)
-    ug = np.asarray(cm.ugrp).reshape(-1, 8)
-    q = np.zeros(T.shape)
-    for k in range(cm.D):
-        _, _, n_grp, grp_off, nI, tab_off, dbl_off, flags = (int(v) for v in uc[k])
-        cd = U[dbl_off:]
-        own1 = 0.0
-        if flags & UCF_OWN:
-            fl = int(ug[grp_off + n_grp, 1])
-            assert not (fl & PLAN_HF) and ((fl >> 24) & 15) <= 1, 'own terms beyond a linear one: extend this tool'
-            own1 = cd[4 + U_GSTRIDE * n_grp + U_GHALF + 1]
-        t = T[:, k]
-        d1, d2 = np.full(t.shape, own1), np.zeros(t.shape)
-        if nI > 0:
-            sp_a, sp_b, sp_ds = cd[1], cd[2], cd[3]
-            u = t * sp_b + sp_a
-            fl_ = np.floor(np.clip(u, -1.0, nI - 2.0))
-            s_ = 2.0 * (u - fl_) - 1.0
-            tab = U[tab_off:tab_off + nI * U_TSTRIDE].reshape(nI, U_TSTRIDE)[:, :12]
-            for n in range(len(t)):
-                P = np.polynomial.Polynomial(tab[int(fl_[n]) + 1])
-                d1[n] += P.deriv(1)(s_[n]) * sp_ds
-                d2[n] += P.deriv(2)(s_[n]) * sp_ds * sp_ds
-        q[:, k] = d2 / d1
-    return q
+    """m''(t) / m'(t) of every component at the raw samples T (rows x D), from the U section of the current coefficient vector
+    (the section's layout lives in tests/uform_section.py, with the tests that hold it to mpmath)."""
+    from tests import uform_section
+    return uform_section.quotient(tm, T)
 
 
 def main(names):
