@@ -592,6 +592,31 @@ int ttm_inverse_newton(const ttm_program* p, const double* coef, const double* f
 int ttm_score(const ttm_program* p, const double* coef, const double* fold, const double* Xsoa, int64_t ldx, int64_t N,
               double* Gsoa, int64_t ldg, const double* g_scale, const double* ld_affine, void* stream);
 
+/* ---- a gradient pulled through the map: the solve with the transposed Jacobian (no counterpart in the reference) ------------
+ * For the components [k0, k1) of a separable map with a U-form given the columns in front, with J = dS/du restricted to that
+ * block (J_kk = m_k'(u_c(k)), J_jk = f_jk'(u_c(k)) for j > k; c(k) = d_cols - D + k the column of component k):
+ *   W = J^-T ( g_scale * G - [logdet] l ),     l_k = m_k''(u_c(k)) / m_k'(u_c(k))
+ * per sample, by back substitution from component k1 - 1 down to k0 (csrc/ttm_pull.h: u_pull_row).  With G = grad_x log p of a
+ * density p on x, g_scale = sigma of the own columns (G in raw coordinates) and logdet = 1, W is the gradient with respect to
+ * z of the logarithm of the pullback p(T(z)) |det grad T(z)|, T = S^-1, at z = S(u): what a Langevin or Hamiltonian move in
+ * reference space needs.
+ *   Xsoa    : the (standardised) samples, d_cols columns, column-major; conditioning columns and components in front of k0 are
+ *             held fixed
+ *   Gsoa    : Gsoa[i * ldg + n] = the gradient's entry for component k0 + i of sample n (k1 - k0 columns)
+ *   g_scale : (nullable, k1 - k0 doubles) factor on column i of G; none: 1
+ *   logdet  : != 0 subtracts l
+ *   Wsoa    : Wsoa[i * ldw + n] = W of component k0 + i (k1 - k0 columns).  May be exactly Gsoa with ldw = ldg (in place: the
+ *             same bits as out of place).
+ * A non-finite sample or gradient makes the entries of its row that depend on it non-finite and leaves every other row alone;
+ * m' = 0 gives what IEEE division gives.  Rows [0, N) of Wsoa's k1 - k0 columns are written and nothing else.
+ * One launch of k_pull_gradient_u (one row per thread, no LDS), graph-capturable.  Pointers and leading dimensions as
+ * ttm_score.  TTM_E_UNSUPPORTED: the map is not separable or has no U-form; TTM_E_ARG: null or misaligned pointers, odd or
+ * short leading dimensions, N < 1 or N >= 2^28, a component range outside 0 <= k0 < k1 <= D, Wsoa overlapping Xsoa, or
+ * overlapping Gsoa without being it.                                                                                       */
+int ttm_pull_gradient(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1,
+                      const double* Xsoa, int64_t ldx, int64_t N, const double* Gsoa, int64_t ldg, const double* g_scale,
+                      int32_t logdet, double* Wsoa, int64_t ldw, void* stream);
+
 /* ---- log-density and score of an integrated-rectifier map (no counterpart in the reference) ------------------------
  * Per sample, with c_k the own column of component k (csrc/ttm_logdensity.h):
  *   logp[n]            = sum_k [ -1/2 S_k(u)^2 + log( (r(g_k(u)) + delta) g_scale[k] ) ]      (without the -D/2 log 2 pi)
@@ -900,6 +925,38 @@ int ttm_mh_step_tempered(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc,
                          double* Znext, int64_t ldzn, double rho, double beta, double* Xrec, int64_t ldxr, int32_t* n_acc,
                          int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
                          uint32_t draw_propose, int64_t row0, void* stream);
+
+/* ttm_mh_step_langevin: the tempered step with a gradient-informed proposal (pCN-Langevin in reference space).  The chain's
+ * target in z is phi(z) w(x(z))^beta; with W = grad_z log of the pulled-back target density (ttm_pull_gradient) the gradient of
+ * log w is d = z + W, and the proposal is
+ *   z' = rho z + kappa d + s xi,     kappa = (1 - rho) beta (the caller's),     s = sqrt((1 - rho)(1 + rho)).
+ * It takes the arguments of ttm_mh_step_tempered, then the state's W (Wcur, ncols columns, updated in place as Zcur), the
+ * proposal's (Wprop), the correction of the acceptance ratio (corr, N doubles: ttm_langevin_corr) and kappa.  Three differences:
+ *   1. with corr given the decision is  accept = lp > -inf && c > -inf && (lc == -inf || log(u) < beta * (lp - lc) + c),
+ *      c = corr[n]: the product rounds, then the sum rounds (no FMA).  A NaN or +inf c is a BAD proposal as such a weight is.
+ *   2. an accepted row takes its row of Wprop into Wcur, together with Z and X.
+ *   3. Znext = fma(rho, z, fma(kappa, z + w, s xi_j)) with z, w the values of Zcur, Wcur after the decision; Zcur is read
+ *      at rho = 0 too.
+ * With Wcur == NULL and Wprop == NULL (then corr == NULL) every output has the bits of ttm_mh_step_tempered, which is this
+ * call; that instantiation of the kernel is reported as k_mh_step, the one with W as k_mh_step<drift>.
+ * TTM_E_ARG: as ttm_mh_step_tempered, and one of Wcur / Wprop without the other, ldwc or ldwp < N, corr without an accept
+ * phase or without the W matrices, kappa not finite.                                                                      */
+int ttm_mh_step_langevin(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out,
+                         const double* Zprop, int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop,
+                         double* Znext, int64_t ldzn, double rho, double beta, double* Xrec, int64_t ldxr, int32_t* n_acc,
+                         int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed, uint32_t draw_accept,
+                         uint32_t draw_propose, int64_t row0, double* Wcur, int64_t ldwc, const double* Wprop, int64_t ldwp,
+                         const double* corr, double kappa, void* stream);
+/* ttm_langevin_corr: the correction c of the step above, per row n < N over ncols columns, with d = z + w, d' = z' + w',
+ * a = z' - rho z, b = z - rho z' (each one FMA) and s^2 = (1 - rho)(1 + rho):
+ *   corr[n] = kappa [ sum_j (b_j d'_j - a_j d_j) + (kappa / 2) sum_j (d_j^2 - d'_j^2) ] / s^2
+ *           = log N(z; mu(z'), s^2) - log N(z'; mu(z), s^2) + log phi(z') - log phi(z),     mu(z) = rho z + kappa d(z)
+ * - two running sums over the columns in ascending order, the division last; 0 at kappa = 0.  One launch of k_langevin_corr
+ * (one thread per row pair; no alignment beyond 8 bytes).  TTM_E_ARG: a null pointer, N < 1, ncols < 1, a leading dimension
+ * < N, rho NaN or |rho| >= 1, kappa not finite.                                                                            */
+int ttm_langevin_corr(const double* Zcur, int64_t ldzc, const double* Wcur, int64_t ldwc, const double* Zprop, int64_t ldzp,
+                      const double* Wprop, int64_t ldwp, double rho, double kappa, int64_t N, int32_t ncols, double* corr,
+                      void* stream);
 
 /* ---- optimisers -----------------------------------------------------------------------------------------
  * TM:3108-3114 (scipy.optimize.minimize, method 'L-BFGS-B': maxcor 10, ftol 2.22e-9, gtol 1e-5, maxls 20) as a host

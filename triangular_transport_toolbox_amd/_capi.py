@@ -84,6 +84,8 @@ _SIGNATURES = {
     'ttm_inverse_logdensity': (ctypes.c_int, [ctypes.POINTER(ttm_program), c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64,
                                               c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'ttm_score': (ctypes.c_int,[ctypes.POINTER(ttm_program), c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'ttm_pull_gradient': (ctypes.c_int, [ctypes.POINTER(ttm_program), c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_i64,
+                                         c_vp]),
     'ttm_logdensity': (ctypes.c_int, [ctypes.POINTER(ttm_program), c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     'ttm_reduce_work_size': (c_i64, [c_i32]),
     'ttm_objective': (ctypes.c_int, [ctypes.POINTER(ttm_program), c_i32, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
@@ -114,6 +116,10 @@ _SIGNATURES = {
                                    c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_i64, c_vp]),
     'ttm_mh_step_tempered': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_vp, c_i64,
                                             c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_i64, c_vp]),
+    'ttm_mh_step_langevin': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_dbl, c_dbl, c_vp, c_i64,
+                                            c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_i64, c_vp, c_i64, c_vp,
+                                            c_i64, c_vp, c_dbl, c_vp]),
+    'ttm_langevin_corr': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_dbl, c_dbl, c_i64, c_i32, c_vp, c_vp]),
     'ttm_temper_scan': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     'ttm_signal': (ctypes.c_int, [c_vp, c_dbl, c_vp]),
     'ttm_lbfgsb_minimize': (ctypes.c_int, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),

@@ -3212,8 +3212,17 @@ __global__ __launch_bounds__(256) void k_resample(const uint64_t* __restrict__ c
 // One Metropolis-Hastings step in reference space (ttm_mh_step; csrc/ttm_mcmc.h): thread i owns pair number i of the window of
 // global rows, as in k_normal_fill, and walks the columns blockIdx.y, blockIdx.y + gridDim.y, ...  Every column group decides
 // the pair for itself from logw_cur / logw_prop, which no workgroup of the launch writes; group 0 writes logw_out and the counts.
+// DRIFT: the Langevin step (ttm_mh_step_langevin with its W matrices); the plain instantiation is the kernel the two other entry
+// points always had.
+template <bool DRIFT>
 __global__ __launch_bounds__(256) void k_mh_step(const MhStep a) {
-    mh_step_pair(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int)blockIdx.y, (int)gridDim.y);
+    mh_step_pair<DRIFT>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int)blockIdx.y, (int)gridDim.y);
+}
+
+// The correction of the Langevin step (ttm_langevin_corr; csrc/ttm_mcmc.h): thread i owns the rows 2 i and 2 i + 1 and walks the
+// columns in ascending order, four 16-byte loads per column.
+__global__ __launch_bounds__(256) void k_langevin_corr(const LangevinCorr a) {
+    langevin_corr_pair(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // The weight summaries of C tempered copies of logw (ttm_temper_scan; csrc/ttm_smc.h).  One workgroup per tile of RS_TILE rows
@@ -4312,6 +4321,38 @@ int ttm_score(const ttm_program* p, const double* coef, const double* fold, cons
     return check_launch("k_score_u");
 }
 
+// A gradient pulled through the map (include/ttm.h: ttm_pull_gradient; csrc/ttm_pull.h): u_pull_row, one row per thread, the
+// back substitution accumulated in the output buffer (each thread reads back what it alone wrote).  The shape of k_score_u.
+struct PullW {
+    double* W; int64_t ld, n;
+    __device__ double get(int i) const { return W[(int64_t)i * ld + n]; }
+    __device__ void set(int i, double v) { W[(int64_t)i * ld + n] = v; }
+};
+// (G and W are not `restrict`: they may be one matrix)
+__global__ __launch_bounds__(256) void k_pull_gradient_u(const int* __restrict__ ucomp, const int* __restrict__ ugrp, const double* __restrict__ U,
+                                                         int E, int k0, int k1, const double* __restrict__ X, int64_t ldx, int64_t N, const double* G,
+                                                         int64_t ldg, const double* __restrict__ g_scale, int logdet, double* W, int64_t ldw) {
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
+        const ScoreX xa{X, ldx, n}, ga{G, ldg, n};
+        PullW wa{W, ldw, n};
+        u_pull_row((cint_p)ucomp, (cint_p)ugrp, (cdbl_p)U, U, E, k0, k1, xa, ga, (cdbl_p)g_scale, logdet != 0, wa);
+    }
+}
+
+int ttm_pull_gradient(const ttm_program* p, const double* coef, const double* fold, int32_t k0, int32_t k1, const double* Xsoa, int64_t ldx, int64_t N,
+                      const double* Gsoa, int64_t ldg, const double* g_scale, int32_t logdet, double* Wsoa, int64_t ldw, void* stream) {
+    int rc = validate(p, k0, k1);
+    if (rc) return rc;
+    if (!pull_args_ok(coef, fold, Xsoa, ldx, N, k1 - k0, p->d_cols, Gsoa, ldg, Wsoa, ldw))
+        return set_err(TTM_E_ARG, "ttm_pull_gradient: bad arguments (null or misaligned pointers, odd or short leading dimensions, N < 1, W overlapping X or part of G)%s");
+    if (p->monotonicity != TTM_MONO_SEPARABLE || !u_on(p))
+        return set_err(TTM_E_UNSUPPORTED, "ttm_pull_gradient: %s", p->monotonicity != TTM_MONO_SEPARABLE ? "the map is not separable" : "the map has no U-form");
+    const double* U = fold + fold_base_size(p);
+    hipLaunchKernelGGL(k_pull_gradient_u, dim3(grid_for(N, 256)), dim3(256), 0, (hipStream_t)stream, p->ucomp, p->ugrp, U, (int)(p->d_cols - p->D), (int)k0,
+                       (int)k1, Xsoa, ldx, N, Gsoa, ldg, g_scale, (int)logdet, Wsoa, ldw);
+    return check_launch("k_pull_gradient_u");
+}
+
 // Log-density and score of an integrated-rectifier map: int_score_row (csrc/ttm_logdensity.h), one row per thread through all
 // components; the row's score columns are accumulated in the output buffer (each thread reads back what it alone wrote), the
 // log-density in a register.  No reductions, no atomics.  The generic table walk, shaped as k_objective: term tables and
@@ -4802,8 +4843,18 @@ int ttm_mh_step_tempered(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc,
                          int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double beta,
                          double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed,
                          uint32_t draw_accept, uint32_t draw_propose, int64_t row0, void* stream) {
+    // the step without drift: the plain instantiation of the kernel
+    return ttm_mh_step_langevin(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, beta, Xrec, ldxr, n_acc,
+                                n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0, nullptr, N, nullptr, N, nullptr, 0.0, stream);
+}
+
+int ttm_mh_step_langevin(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc, const double* logw_cur, double* logw_out, const double* Zprop,
+                         int64_t ldzp, const double* Xprop, int64_t ldxp, const double* logw_prop, double* Znext, int64_t ldzn, double rho, double beta,
+                         double* Xrec, int64_t ldxr, int32_t* n_acc, int32_t* n_bad, int64_t N, int32_t ncols, int32_t col0, uint64_t seed,
+                         uint32_t draw_accept, uint32_t draw_propose, int64_t row0, double* Wcur, int64_t ldwc, const double* Wprop, int64_t ldwp,
+                         const double* corr, double kappa, void* stream) {
     const MhStep a = mh_step_pack(Zcur, ldzc, Xcur, ldxc, logw_cur, logw_out, Zprop, ldzp, Xprop, ldxp, logw_prop, Znext, ldzn, rho, beta, Xrec, ldxr,
-                                  n_acc, n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0);
+                                  n_acc, n_bad, N, ncols, col0, seed, draw_accept, draw_propose, row0, Wcur, ldwc, Wprop, ldwp, corr, kappa);
     if (!mh_step_args_ok(a)) return set_err(TTM_E_ARG, "ttm_mh_step: bad arguments%s");
     const int64_t gx = (normal_fill_pairs(N, row0) + 255) / 256;
     if (gx > 0x7fffffff) return set_err(TTM_E_LIMIT, "ttm_mh_step: %s%lld rows are more than one launch covers", "", (long long)N);
@@ -4811,8 +4862,22 @@ int ttm_mh_step_tempered(double* Zcur, int64_t ldzc, double* Xcur, int64_t ldxc,
     int64_t gy = (32 * (int64_t)device_info().cus + gx - 1) / gx;
     gy = gy < 1 ? 1 : (gy > ncols ? ncols : gy);
     if (gy > 65535) gy = 65535;
-    hipLaunchKernelGGL(k_mh_step, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, a);
+    if (Wcur) {
+        hipLaunchKernelGGL(k_mh_step<true>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, a);
+        return check_launch("k_mh_step<drift>");
+    }
+    hipLaunchKernelGGL(k_mh_step<false>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("k_mh_step");
+}
+
+int ttm_langevin_corr(const double* Zcur, int64_t ldzc, const double* Wcur, int64_t ldwc, const double* Zprop, int64_t ldzp, const double* Wprop,
+                      int64_t ldwp, double rho, double kappa, int64_t N, int32_t ncols, double* corr, void* stream) {
+    const LangevinCorr a = langevin_corr_pack(Zcur, ldzc, Wcur, ldwc, Zprop, ldzp, Wprop, ldwp, rho, kappa, N, ncols, corr);
+    if (!langevin_corr_args_ok(a)) return set_err(TTM_E_ARG, "ttm_langevin_corr: bad arguments%s");
+    const int64_t gx = ((N + 1) / 2 + 255) / 256;
+    if (gx > 0x7fffffff) return set_err(TTM_E_LIMIT, "ttm_langevin_corr: %s%lld rows are more than one launch covers", "", (long long)N);
+    hipLaunchKernelGGL(k_langevin_corr, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("k_langevin_corr");
 }
 
 int ttm_map_columns(const double* in, int64_t ldi, const int32_t* src, const double* scale, const double* shift, int32_t ncols,

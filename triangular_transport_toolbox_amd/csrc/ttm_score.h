@@ -192,3 +192,6 @@ extern "C" __attribute__((used, visibility("default"))) inline int ttm_score(con
 // ttm_inverse_logdensity - the host test double takes it from there, as the two above)
 #include "ttm_sample_logq.h"
 #endif
+
+// (a gradient pulled through the map - the transposed-Jacobian solve from the same pieces, with its own host-only entry point)
+#include "ttm_pull.h"

@@ -74,6 +74,43 @@ class Proposal:
             return to_dev(logp)
         return target
 
+    def host_gradient(self, grad_log_target_pdf):
+        """A NumPy-convention gradient (N x ncols rows in, N x ncols out) as a device-convention one ((ncols, N) in and out)."""
+        N, ncols, to_dev = self.N, self.ncols, self.tm._to_dev
+
+        def grad(raw):
+            g = np.asarray(grad_log_target_pdf(np.ascontiguousarray(raw.cpu().numpy().T)), dtype=float)
+            if g.shape != (N, ncols):
+                raise ValueError('grad_log_target_pdf must return a %d x %d array' % (N, ncols))
+            return to_dev(np.ascontiguousarray(g.T))
+        return grad
+
+    @staticmethod
+    def autograd_gradient(target):
+        """The gradient of a device-convention target by torch.autograd.grad: one more evaluation of the target per call."""
+        import torch
+
+        def grad(raw):
+            with torch.enable_grad():
+                x = raw.detach().clone().requires_grad_(True)
+                (g,) = torch.autograd.grad(target(x).sum(), x)
+            return g
+        return grad
+
+    def pull(self, grad, W):
+        """W (ncols, ld) = the gradient of the log of the pulled-back target density with respect to z at the rows in Xs: the
+        device-convention `grad` at the raw own columns, then ttm_pull_gradient over [k0, D) in place, with sigma of the own
+        columns as g_scale and the log-determinant term."""
+        import torch
+        tm, N = self.tm, self.N
+        g = grad(self.raw(self.c0))
+        if not isinstance(g, torch.Tensor) or tuple(g.shape) != (self.ncols, N):
+            raise ValueError('grad_log_target_pdf must return a (%d, %d) tensor' % (self.ncols, N))
+        W[:, :N].copy_(g)
+        sigma = tm._ptr(tm._std_d, self.c0) if tm.standardize_samples else None
+        _capi.check(tm._lib.ttm_pull_gradient(tm._pp, tm._ptr(self.coef), tm._ptr(self.coef._ttm_fold), self.k0, tm.D, tm._ptr(self.Xs), self.ldp, N,
+                                              tm._ptr(W), W.shape[1], sigma, 1, tm._ptr(W), W.shape[1], tm._stream()))
+
     def export_own(self, cols, out):
         """The standardised own columns `cols` (column-major, (ncols, ld)) as raw rows into `out` (N x ncols, row-major): ttm_export."""
         tm = self.tm
@@ -81,16 +118,25 @@ class Proposal:
         sd = tm._ptr(tm._std_d, self.c0) if tm.standardize_samples else None
         _capi.check(tm._lib.ttm_export(tm._ptr(cols), cols.shape[1], self.N, 0, self.ncols, mean, sd, tm._ptr(out), tm._stream()))
 
-    def moves(self, target, n, Zcur, Xcur, lw, Zp, n_acc, n_bad, logq, rho, beta, seed64, draw, row0=0, record=None):
+    def moves(self, target, n, Zcur, Xcur, lw, Zp, n_acc, n_bad, logq, rho, beta, seed64, draw, row0=0, record=None, grad=None, Wcur=None, Wp=None,
+              corr=None):
         """n Metropolis-Hastings moves of the state (Zcur, Xcur: (ncols, ld), updated in place) at the exponent beta (1.0: the plain
         step): n + 1 launches of ttm_mh_step_tempered - the first proposes, each later one decides move t and proposes move t + 1,
         the last decides - and between two of them the inverse with its log-density and the target.  lw: two vectors of N doubles,
         lw[0] the current log-weights, written by turns; Zp: two (ncols, ld) matrices for the proposals; logq: N doubles of
         scratch.  Move t takes draw + t for its innovations and accept uniforms.  record(t): the (ncols, ld) matrix that receives
-        the own columns after move t, or None.  Returns the vector of lw that holds the log-weights afterwards; n = 0: nothing."""
+        the own columns after move t, or None.  Returns the vector of lw that holds the log-weights afterwards; n = 0: nothing.
+        grad (a device-convention gradient of the target): Langevin moves, ttm_mh_step_langevin with kappa = (1 - rho) beta -
+        Wcur: the state's pulled gradient ((ncols, ld), updated in place), Wp: a matrix for the proposal's, corr: N doubles of
+        scratch; between two launches the inverse with its log-density, the target, the pull (pull) and ttm_langevin_corr.
+        Without grad: the calls above and nothing else."""
         tm, N, k0, ncols, ld = self.tm, self.N, self.k0, self.ncols, Zcur.shape[1]
         ptr, step, st = tm._ptr, tm._lib.ttm_mh_step_tempered, tm._stream()
         xprop = ptr(self.Xs, self.c0 * self.ldp)         # (where the inverse leaves the proposal's own columns)
+        kappa = (1.0 - rho) * beta
+        drift = () if grad is None else (ptr(Wcur), ld, ptr(Wp), ld)
+        if grad is not None:
+            step = tm._lib.ttm_mh_step_langevin
         lw, lwp = list(lw), None
         for t in range(n + 1 if n else 0):
             accept, propose = t >= 1, t < n
@@ -99,10 +145,14 @@ class Proposal:
             _capi.check(step(ptr(Zcur), ld, ptr(Xcur), ld, ptr(lw[0]), ptr(lw[1]) if accept else None,
                              ptr(Zp[(t - 1) & 1]) if accept else None, ld, xprop if accept else None, self.ldp,
                              ptr(lwp) if accept else None, ptr(zn), ld, rho, beta, ptr(rec), ld, ptr(n_acc), ptr(n_bad), N, ncols, k0,
-                             seed64, draw + t if accept else 0, draw + t + 1 if propose else 0, row0, st))
+                             seed64, draw + t if accept else 0, draw + t + 1 if propose else 0, row0,
+                             *(drift + ((ptr(corr) if accept else None, kappa) if drift else ()) + (st,))))
             if accept:
                 lw.reverse()
             if propose:
                 self.inverse_logq(zn, logq)
                 lwp = self.weigh(target, logq)
+                if grad is not None:
+                    self.pull(grad, Wp)
+                    _capi.check(tm._lib.ttm_langevin_corr(ptr(Zcur), ld, ptr(Wcur), ld, ptr(zn), ld, ptr(Wp), ld, rho, kappa, N, ncols, ptr(corr), st))
         return lw[0]

@@ -1390,6 +1390,47 @@ class transport_map():
         G = self.score_device(Xs, N, coef, g_scale=g_scale, ld_affine=ld_affine)
         return self._export(G, N, 0, D, False)
 
+    def pull_gradient_device(self, Xs, N, G, k0=0, g_scale=None, logdet=True, out=None):
+        """A gradient pulled through the components k0 .. D - 1 of the map (include/ttm.h: ttm_pull_gradient): for the standardised
+        column-major device matrix Xs (d x N) and G ((D - k0, ld), row i the entry of component k0 + i) the (D - k0, ld) tensor
+            W = J^-T (g_scale * G - [logdet] l),   J = dS/du of that block,   l_k = m_k''(u_k) / m_k'(u_k).
+        With G the gradient of log p in raw coordinates, g_scale = X_std of the own columns (a device tensor) and logdet True, W is
+        the gradient with respect to z of log [p(T(z)) |det grad T(z)|], T = S^-1, at z = S(u).  out: the tensor that receives W;
+        it may be G itself.  Separable maps with a univariate form only.  One launch."""
+        coef = self._current(None)
+        why = self._score_unsupported()
+        if why:
+            raise NotImplementedError('gradient pulled through the map: ' + why)
+        W = self._cols(self.D - k0, N) if out is None else out
+        _capi.check(self._lib.ttm_pull_gradient(self._pp, self._ptr(coef), self._ptr(coef._ttm_fold), int(k0), self.D, self._ptr(Xs), Xs.shape[1], N,
+                                                self._ptr(G), G.shape[1], self._ptr(g_scale), 1 if logdet else 0, self._ptr(W), W.shape[1],
+                                                self._stream()))
+        return W
+
+    def pull_gradient(self, X, G, X_star=None, logdet=True):
+        """The gradient of a log-density on x carried to the reference space of the map, for a user's own MALA or HMC there: X the
+        raw samples (N x (D - k0), with the columns in front as X_star - the conditioning shapes of evaluate_pullback_score),
+        G an N x (D - k0) array of d log p / dx in raw coordinates.  Returns the N x (D - k0) array of the gradient with respect
+        to z of log [p(T(z)) |det grad T(z)|], T = S^-1, at z = map(X) (logdet False: J^-T sigma G alone).  Separable maps with a
+        univariate form only."""
+        why = self._score_unsupported()
+        if why:
+            raise NotImplementedError('pull_gradient: ' + why)
+        if not self.standardize_samples:
+            raise NotImplementedError('pull_gradient: standardize_samples = False (the map ignores X)')
+        if X_star is not None:
+            X = np.column_stack((X_star, X))
+        X, G = np.asarray(X, dtype=float), np.asarray(G, dtype=float)
+        d = self._cm.d_cols
+        if G.ndim != 2 or X.ndim != 2 or G.shape[0] != X.shape[0] or not 1 <= G.shape[1] <= self.D:
+            raise ValueError('G must be an N x (D - k0) array with the rows of X')
+        ncols = G.shape[1]
+        Xs, N = self._samples_for(X)
+        sigma = self._to_dev(np.ascontiguousarray(np.asarray(self.X_std, dtype=float)[d - ncols:d]))
+        W = self._import(G, False)
+        self.pull_gradient_device(Xs, N, W, k0=self.D - ncols, g_scale=sigma, logdet=logdet, out=W)
+        return self._export(W, N, 0, ncols, False)
+
     def logdensity_device(self, Xs, N, coef=None, logp=None, G=None, g_scale=None):
         """Log-density of the pullback of an integrated-rectifier map and its score for a standardised column-major device
         matrix Xs (d x N) -> (logp (N), G (D x N)):  logp[n] = sum_k [ -1/2 S_k(u)^2 + log((r(g_k) + delta) g_scale[k]) ] (without
@@ -1789,7 +1830,8 @@ class transport_map():
     # ---- map-preconditioned Metropolis-Hastings (no counterpart in the reference): chains in the reference space of the map, where
     # the target is close to a standard normal; the step is one launch (ttm_mh_step, k_mh_step) - include/ttm.h, DESIGN.md section 4 --
 
-    def mcmc_device(self, log_target_pdf, chains, steps, Xs=None, rho=0.0, burn=0, thin=1, seed=0, draw=None, row0=0, init=None, k0=0):
+    def mcmc_device(self, log_target_pdf, chains, steps, Xs=None, rho=0.0, burn=0, thin=1, seed=0, draw=None, row0=0, init=None, k0=0,
+                    grad_log_target_pdf=None):
         """`chains` independent Metropolis-Hastings chains (one per row) of `steps` steps in the reference space of the map,
         device-resident.  With S the map of the components k0 .. D - 1 given the columns in front, q the density of the map's
         draws and w = p / q, step t proposes
@@ -1816,7 +1858,17 @@ class transport_map():
         alternate_root_finding = False, or an integrated-rectifier map, makes the step exact to the root tolerance.
         Returns (trace, state): trace a (kept, D - k0, ld) device tensor, the STANDARDISED own columns after the steps
         burn + thin, burn + 2 thin, ... <= steps; state a dict (Z, X, logw, n_acc, n_bad on the device; steps, draws, seed,
-        row0) that init= takes."""
+        row0) that init= takes.
+        grad_log_target_pdf: Langevin moves (pCN-Langevin in reference space; separable maps with a univariate form).  A callable
+        that gets the raw own coordinates as log_target_pdf does and returns d log p / dx as a (D - k0, chains) device tensor,
+        or 'autograd' (log_target_pdf is differentiated with torch.autograd.grad).  With W the gradient pulled to z
+        (ttm_pull_gradient) and d = z + W the gradient of log w, step t proposes
+            z' = rho z + (1 - rho) d + sqrt(1 - rho^2) xi
+        and accepts with the ratio above times exp(c), c the correction of ttm_langevin_corr: steps + 1 launches of
+        ttm_mh_step_langevin, and between two of them the inverse, the target, the gradient's pull and the correction.  If the
+        fit is exact, d = 0 and the moves are those without a gradient.  The initial state gets its W from one pull (a
+        non-finite one raises ValueError in the same read-back); state gains 'W', and a continuation takes it from there (a
+        state without it: one pull; without a gradient it is ignored)."""
         torch = _torch()
         N, steps, burn, thin, k0, row0 = int(chains), int(steps), int(burn), int(thin), int(k0), int(row0)
         rho = float(rho)
@@ -1858,6 +1910,19 @@ class transport_map():
             init = np.asarray(init, dtype=float)
             if init.shape != (N, ncols):
                 raise ValueError('init must be a %d x %d array or the state of an earlier run' % (N, ncols))
+        grad = grad_log_target_pdf
+        if grad is not None:
+            why = self._score_unsupported()
+            if why:
+                raise NotImplementedError('Langevin moves: ' + why)
+            if isinstance(grad, str):
+                if grad != 'autograd':
+                    raise ValueError("grad_log_target_pdf must be a callable or 'autograd'")
+                grad = Proposal.autograd_gradient(log_target_pdf)
+            if cont and 'W' in init:
+                v = init['W']
+                if not isinstance(v, torch.Tensor) or tuple(v.shape) != (ncols, ld) or v.dtype != torch.float64 or v.device.type != self._dev.type or not v.is_contiguous():
+                    raise ValueError('init is not the state of %d chains of %d components' % (N, ncols))
         P = Proposal(self, N, k0, Xs)
         c0, d = P.c0, P.d
         if draw is None:
@@ -1866,6 +1931,15 @@ class transport_map():
         if cont:
             Zcur, Xcur, logw = init['Z'].clone(), init['X'].clone(), init['logw'].clone()
             n_acc, n_bad = init['n_acc'].clone(), init['n_bad'].clone()
+            Wcur = None
+            if grad is not None and 'W' in init:
+                Wcur = init['W'].clone()
+            elif grad is not None:                       # (a state of a run without a gradient: one pull at its rows)
+                P.Xs[c0:d, :N].copy_(Xcur[:, :N])
+                Wcur = self._cols(ncols, N, zero=True)
+                P.pull(grad, Wcur)
+                if not bool(torch.isfinite(Wcur[:, :N]).all().item()):
+                    raise ValueError('an initial pulled gradient is not finite')
         else:
             if init is not None:
                 init_d = self._to_dev(init)              # (held by name: a temporary would be freed before the import reads it)
@@ -1879,20 +1953,32 @@ class transport_map():
             Xcur = self._cols(ncols, N, zero=True)       # (its own matrix of leading dimension ld, whatever the width of Xs)
             Xcur[:, :N].copy_(P.Xs[c0:d, :N])
             logw = P.weigh(log_target_pdf, logq)
-            if bool((torch.isnan(logw) | (logw == float('inf'))).any().item()):       # (the one read-back of the run)
+            Wcur = None
+            bad = (torch.isnan(logw) | (logw == float('inf'))).any()
+            if grad is not None:
+                Wcur = self._cols(ncols, N, zero=True)
+                P.pull(grad, Wcur)
+                bad = torch.stack((bad, ~torch.isfinite(Wcur[:, :N]).all()))
+            bad = bad.reshape(-1).tolist()                                            # (the one read-back of the run)
+            if bad[0]:
                 raise ValueError('an initial log-weight is NaN or +inf')
+            if bad[-1] and grad is not None:
+                raise ValueError('an initial pulled gradient is not finite')
             n_acc, n_bad, done = self._zeros(N, dtype=torch.int32), self._zeros(N, dtype=torch.int32), 0
         Zp = (self._cols(ncols, N), self._cols(ncols, N))
         spare = self._empty(N)
         trace = self._empty(kept, ncols, ld)
+        langevin = {} if grad is None else dict(grad=grad, Wcur=Wcur, Wp=self._cols(ncols, N, zero=True), corr=self._empty(N))
         logw = P.moves(log_target_pdf, steps, Zcur, Xcur, (logw, spare), Zp, n_acc, n_bad, logq, rho, 1.0, seed64, draw0, row0,
-                       record=lambda t: trace[(t - burn) // thin - 1] if (t > burn and (t - burn) % thin == 0) else None)
+                       record=lambda t: trace[(t - burn) // thin - 1] if (t > burn and (t - burn) % thin == 0) else None, **langevin)
         state = dict(Z=Zcur, X=Xcur, logw=logw, n_acc=n_acc, n_bad=n_bad, steps=done + steps, draws=(draw0, draw0 + steps),
                      seed=seed64, row0=row0)
+        if grad is not None:
+            state['W'] = Wcur
         return trace, state
 
     def sample_mcmc(self, log_target_pdf, chains, steps, X_star=None, rho=0.0, burn=0, thin=1, seed=0, draw=None, row0=0, init=None,
-                    target_on_device=False):
+                    target_on_device=False, grad_log_target_pdf=None):
         """Map-preconditioned Metropolis-Hastings (mcmc_device, which states the algorithm and the draw numbers): `chains`
         independent chains, one per row, of `steps` steps towards the density exp(log_target_pdf), with the fitted map as the
         preconditioner - where importance resampling (sample_importance) loses its effective sample size to a mediocre fit, a
@@ -1911,13 +1997,22 @@ class transport_map():
         shape or a state that is incomplete or continued with another seed or row0 than its own, a target that does not return
         `chains` values, an initial log-weight that is NaN or +inf (-inf is allowed: such a chain accepts its first admissible
         proposal).
-        With the table inverse the chain targets the density up to the table's round-trip error; see mcmc_device."""
+        With the table inverse the chain targets the density up to the table's round-trip error; see mcmc_device.
+        grad_log_target_pdf: Langevin moves, as mcmc_device states them - the gradient of log_target_pdf in its own convention
+        (a chains x (D - k0) array in, the same shape out; target_on_device True: a (D - k0, chains) device tensor in and out,
+        or 'autograd').  ValueError for a gradient of another shape and for 'autograd' with a host target."""
         N = int(chains)
         if N < 1:
             raise ValueError('chains must be at least 1')
         P = Proposal.from_star(self, N, X_star, density=False)           # (mcmc_device makes its own, with the density's part)
         target = log_target_pdf if target_on_device else P.host_target(log_target_pdf)
-        trace, state = self.mcmc_device(target, N, steps, Xs=P.Xs, rho=rho, burn=burn, thin=thin, seed=seed, draw=draw, row0=row0, init=init, k0=P.k0)
+        grad = grad_log_target_pdf
+        if isinstance(grad, str) and not target_on_device:
+            raise ValueError("grad_log_target_pdf = 'autograd' needs a target on the device (target_on_device = True)")
+        if grad is not None and not isinstance(grad, str) and not target_on_device:
+            grad = P.host_gradient(grad)
+        trace, state = self.mcmc_device(target, N, steps, Xs=P.Xs, rho=rho, burn=burn, thin=thin, seed=seed, draw=draw, row0=row0, init=init, k0=P.k0,
+                                        grad_log_target_pdf=grad)
         out = self._empty(trace.shape[0], N, P.ncols)
         for i in range(trace.shape[0]):
             P.export_own(trace[i], out[i])
