@@ -506,6 +506,9 @@ int ttm_inverse_table_build_index(const ttm_program* p, const double* coef, cons
  * the RESIDENT-TABLE IMAGE of every component - search parameters, the window of the table the lookup kernel of banded maps
  * keeps in LDS, its 16-bit bucket index (csrc/ttm_band_image.h) - laid out once here so that ttm_inverse_table copies them
  * into LDS by DMA instead of assembling them per workgroup.  A pure function of the table: passing it changes no result.
+ * Where the launch plan allows (option band_slopes, csrc/ttm_band_image.h) an image also carries the slope of every interval of its
+ * window, formed from the table and pts as the lookup forms it per row: pts must then be the abscissae that ttm_inverse_table's
+ * h_y_affine describes, bit for bit (THE ABSCISSAE above - the same condition under which h_y_affine may be passed at all).
  * ttm_inverse_table_image_doubles returns 0 when the map / table geometry has no such kernel (img must then be NULL).       */
 int64_t ttm_inverse_table_image_doubles(const ttm_program* p, int32_t k0, int32_t k1, int32_t T, int32_t nb);
 /* ---- forward map + table inverse of the image in ONE launch (maps of at most four components, N >= 65 536) -----------------

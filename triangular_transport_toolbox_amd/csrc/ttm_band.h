@@ -42,11 +42,12 @@ int forward(const ttm_program* p, const double* U, int k0, int k1, const double*
 // img: the resident-table images of the components (image_plan; written by k_table_build_index) or nullptr
 // resident: option band_resident - the cache policy of k_band_inverse_ring's column streams (csrc/ttm_band_policy.h)
 // full_tiles, zdma, ring_slots: options band_full_tiles, band_zdma, band_ring_slots - the cut of a k_band_inverse_ring launch, its
-// ZD and the slots of its ring (same header)
+// ZD and the slots of its ring (same header); slopes: option band_slopes - images with interval slopes where the plan allows
+// (csrc/ttm_band_image.h: band_ring_plan), the value the images were built under
 int inverse(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx,
             int64_t N, const double* tab_x, int T, const double* y_affine, const double* tmin, const double* tmax, const int32_t* bkt,
             int nb, const double* img, int img_doubles, int cus, size_t lds_per_cu, int window, int block, int resident, int full_tiles, int zdma,
-            int ring_slots, void* stream, const char** kernel_name);
+            int ring_slots, int slopes, void* stream, const char** kernel_name);
 
 // safeguarded Newton root search (sample_newton, csrc/ttm_eval.h: bracket +-2, window doubling, |S - z| <= 1e-9, at most 100
 // trial points) in push form: the monotone part is the component's resident spline (+ its linear own term), no
@@ -79,8 +80,10 @@ int roundtrip(const ttm_program* p, const double* U, int k0, int k1, const doubl
               const char** kernel_name);
 
 // does the table inverse of [k0, k1) take resident-table images (csrc/ttm_band_image.h) for this table geometry?  The window
-// [w0, w0 + W) of every table and the doubles per image (the table-building kernel writes them, `inverse` reads them)
-bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, size_t lds_per_cu, int window, int block, int* w0, int* W, int* tab_slot);
+// [w0, w0 + W) of every table and the doubles per image (the table-building kernel writes them, `inverse` reads them; with the
+// interval slopes where option band_slopes and the plan allow: the doubles per image tell the layout)
+bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, size_t lds_per_cu, int window, int block, int slopes, int* w0, int* W,
+                int* tab_slot);
 
 // TEST HOOK (ttm_math_probe, include/ttm.h): out[i] = f(a[i] [, b[i]]) for the primitives private to csrc/ttm_band.hip -
 // `which` one of TTM_PROBE_BAND_* (the caller has checked it and the pointers; n >= 1).  The pair table is staged by the

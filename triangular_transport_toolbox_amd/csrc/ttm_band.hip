@@ -1222,11 +1222,16 @@ template <int POL, int Q>
 __device__ __forceinline__ void band_zd_request(const char* g, unsigned int lds_wave_base) {
     if (band_z_nt<POL, Q>) band_dma16_nt(g, lds_wave_base); else band_dma16(g, lds_wave_base);
 }
-template <int CLS, int LAG, bool RING = false, int G = 0, int POL = 0, int ZD = 0>
+//
+// SL = 1 (the ring kernel only, ZD = 0): the images carry the slope of every interval (ttm_band_image.h, the slope layout) - the
+// last phase of the search reads {E_lo, y_lo}, x_lo and the slope instead of forming the slope per row from x_hi and y_hi.
+// The outlier path, which reads the table in memory, keeps forming it.
+template <int CLS, int LAG, bool RING = false, int G = 0, int POL = 0, int ZD = 0, int SL = 0>
 __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool full, int kb, int ke, const char* zcol, char* xcol, unsigned int tbase,
                                                   const unsigned int (&roff)[BAND_NS / 2], double (&pend)[BAND_NS][LAG],
                                                   const D2 (&zfirst)[BAND_NS / 2], bool have_first, BandRing* rg = nullptr, unsigned int zq = 0) {
     static_assert(ZD == 0 || (RING && POL == 1), "ZD = 1: the ring kernel under the resident policy");
+    static_assert(SL == 0 || (RING && ZD == 0), "SL = 1: images with slopes, the ring kernel without the column buffers");
     constexpr int DB = cls_db(CLS), DA = cls_da(CLS), PS = rec_stride(CLS, LAG);
     constexpr int NS = BAND_NS, NP = NS / 2, HALF = 2 * BAND_CT;
     cdbl_p rec = cx.P + (int64_t)(kb + LAG) * PS;
@@ -1254,11 +1259,12 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
         band_slots<NP>([&](auto Q) { constexpr int q = decltype(Q)::value; za[q] = band_load2<band_z_nt<POL, q>>(zcol + roff[q]); });
     }
     // interp1d slope form (TM:4062-4065) in the located interval and exp(-x^2/4) = E[i-1] exp(w), w = -delta (y_lo + x) / 4
-    auto interp = [&](double y_lo, double y_hi, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
-        const double dx = fmax(x_hi - x_lo, 1e-300);                          // (tie at a flat start: k_inverse_rt)
-        double rc = __builtin_amdgcn_rcp(dx);
-        rc = fma(fma(-dx, rc, 1.0), rc, rc);
-        const double delta = ((y_hi - y_lo) * rc) * (tgt - x_lo);           // (the abscissae are np.linspace's to the bit: include/ttm.h)
+    // from_image (std::true_type, SL only): the fourth argument IS the interval's slope as the image carries it and x_hi is not read;
+    // std::false_type: it is y_hi and the slope is formed here.  One body, so that both forms share the series below to the letter.
+    auto interp = [&](auto from_image, double y_lo, double y_hi_or_slope, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
+        // (the slope with the tie at a flat start: band_interval_slope; the abscissae are np.linspace's to the bit: include/ttm.h)
+        const double slope = decltype(from_image)::value ? y_hi_or_slope : band_interval_slope(x_lo, x_hi, y_lo, y_hi_or_slope);
+        const double delta = slope * (tgt - x_lo);
         rr = delta + y_lo;
         const double w = (delta * -0.25) * (y_lo + rr);
         double p = fma(kt[0], w, kt[1]);
@@ -1295,7 +1301,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
         double wl, wh, scale, bias;
         { const D2 a = *(const D2*)slot; wl = a.x; wh = a.y; const D2 b = *(const D2*)(slot + 2); scale = b.x; bias = b.y; }
         const lds_p xsl = band_lds(slot + BAND_RT_HDR) - 8 * cx.w0;           // xs indexed by the entry's number in the whole table
-        const lds_p bkl = band_lds(slot + BAND_RT_HDR + cx.Weven);
+        const lds_p bkl = band_lds(slot + BAND_RT_HDR + (SL ? 2 : 1) * cx.Weven);
         const bool deg = __builtin_amdgcn_readfirstlane(((const int*)slot)[10]) != 0;
         const int per = __builtin_amdgcn_readfirstlane(((const int*)slot)[8]);
         double traw[NS], tg[NS], r[NS], E[NS];
@@ -1347,19 +1353,36 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
                 for (int i = 1; i < NC; ++i) qv[e][i] = band_lds_f64_single(q4 + 8 * i);
             }
             D2 ey[NS];
-            double xlo[NS], xhi[NS], yhi[NS];
+            // (two whole bodies, not one with conditions inside: the SL = 0 body is the parent's text, and with it every SL = 0
+            // instantiation keeps the parent's registers and spills - OPTLOG round 16 item 3)
+            if constexpr (SL != 0) {
+                double xlo[NS], slope[NS];
 #pragma unroll
-            for (int e = 0; e < NS; ++e) {
+                for (int e = 0; e < NS; ++e) {
 #pragma unroll
-                for (int i = 0; i < NC; ++i) pos[e] += qv[e][i] < tg[e] ? 1 : 0;
-                ey[e] = band_lds_pair(cx.etab1 + 16 * pos[e]);
-                yhi[e] = band_lds_f64_single(cx.etab1 + 16 * pos[e] + 24);    // (y of entry pos, from the pair behind; measured: a read off the pair's base register is slower)
-                const lds_p xp = xsl + 8 * pos[e];
-                xlo[e] = band_lds_f64(xp - 8);
-                xhi[e] = band_lds_f64_single(xp);
+                    for (int i = 0; i < NC; ++i) pos[e] += qv[e][i] < tg[e] ? 1 : 0;
+                    ey[e] = band_lds_pair(cx.etab1 + 16 * pos[e]);
+                    const lds_p xp = xsl + 8 * pos[e];
+                    xlo[e] = band_lds_f64(xp - 8);
+                    slope[e] = band_lds_f64_single(xp + 8 * cx.Weven);         // (the slope of the interval below entry pos: indexed like xs)
+                }
+#pragma unroll
+                for (int e = 0; e < NS; ++e) interp(std::true_type(), ey[e].y, slope[e], xlo[e], 0.0, ey[e].x, tg[e], r[e], E[e]);
+            } else {
+                double xlo[NS], xhi[NS], yhi[NS];
+#pragma unroll
+                for (int e = 0; e < NS; ++e) {
+#pragma unroll
+                    for (int i = 0; i < NC; ++i) pos[e] += qv[e][i] < tg[e] ? 1 : 0;
+                    ey[e] = band_lds_pair(cx.etab1 + 16 * pos[e]);
+                    yhi[e] = band_lds_f64_single(cx.etab1 + 16 * pos[e] + 24);    // (y of entry pos, from the pair behind; measured: a read off the pair's base register is slower)
+                    const lds_p xp = xsl + 8 * pos[e];
+                    xlo[e] = band_lds_f64(xp - 8);
+                    xhi[e] = band_lds_f64_single(xp);
+                }
+#pragma unroll
+                for (int e = 0; e < NS; ++e) interp(std::false_type(), ey[e].y, yhi[e], xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
             }
-#pragma unroll
-            for (int e = 0; e < NS; ++e) interp(ey[e].y, yhi[e], xlo[e], xhi[e], ey[e].x, tg[e], r[e], E[e]);
         };
         if (per <= 2) search(std::integral_constant<int, 2>());
         else search(std::integral_constant<int, 4>());
@@ -1380,7 +1403,7 @@ __device__ __forceinline__ void band_inverse_tile(const BandInvCtx& cx, bool ful
                         if (xg[mid] < t) a = mid + 1; else b = mid;
                     }
                     const int i = min(max(a, 1), cx.T - 1);
-                    interp((double)(i - 1) * ystep + cx.y0, i == cx.T - 1 ? cx.ylast : (double)i * ystep + cx.y0, xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + cx.y0), t, r[e], E[e]);
+                    interp(std::false_type(), (double)(i - 1) * ystep + cx.y0, i == cx.T - 1 ? cx.ylast : (double)i * ystep + cx.y0, xg[i - 1], xg[i], band_expq_series((double)(i - 1) * ystep + cx.y0), t, r[e], E[e]);
                 }
             }
         }
@@ -1606,7 +1629,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse(const double* __restri
 // POL: the cache policy of the column streams (band_inverse_tile; the host's choice: ttm_band_policy.h)
 // ZD = 1: full tiles take Z through two column buffers in LDS behind the {E_i, y_i} pairs (band_inverse_tile; the ring has
 // fewer slots: band_ring_plan_with), partial tiles run the code of ZD = 0
-template <int CLS, int LAG, int G, int POL = 0, int ZD = 0>
+// SL = 1: the images carry the interval slopes (band_inverse_tile; the plan's choice: band_ring_plan) - beside ZD = 0 only
+template <int CLS, int LAG, int G, int POL = 0, int ZD = 0, int SL = 0>
 __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __restrict__ U_, int64_t p_off, int k0, int k1, int kcol0,
                                                                const double* __restrict__ Z, int64_t ldz, double* X, int64_t ldx, int64_t N,
                                                                const double* __restrict__ tab_x, int T, double y0, double ystep, double ylast,
@@ -1720,7 +1744,7 @@ __global__ __launch_bounds__(BAND_CT) void k_band_inverse_ring(const double* __r
                 band_inverse_tile<CLS, LAG, true, G, POL, 1>(cx, true, k0, k1, (const char*)Z, (char*)X + (int64_t)kcol0 * ldxb, tbase, roff, pend, zfirst, false, &rg, zq);
             }
         } else
-        band_inverse_tile<CLS, LAG, true, G, POL>(cx, full, k0, k1, (const char*)Z, (char*)X + (int64_t)kcol0 * ldxb, tbase, roff, pend, zfirst, tile == 0, &rg);
+        band_inverse_tile<CLS, LAG, true, G, POL, 0, SL>(cx, full, k0, k1, (const char*)Z, (char*)X + (int64_t)kcol0 * ldxb, tbase, roff, pend, zfirst, tile == 0, &rg);
     }
 }
 
@@ -1767,10 +1791,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_inverse(const double* __re
     __builtin_amdgcn_sched_barrier(0);
     // interp1d slope form (TM:4062-4065) in the located interval and exp(-x^2/4) = E[i-1] exp(w), w = -delta (y_lo + x) / 4
     auto interp = [&](double y_lo, double y_hi, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
-        const double dx = fmax(x_hi - x_lo, 1e-300);                          // (tie at a flat start: k_inverse_rt)
-        double rc = __builtin_amdgcn_rcp(dx);
-        rc = fma(fma(-dx, rc, 1.0), rc, rc);
-        const double delta = ((y_hi - y_lo) * rc) * (tgt - x_lo);           // (the abscissae are np.linspace's to the bit: include/ttm.h)
+        // (the slope with the tie at a flat start: band_interval_slope; the abscissae are np.linspace's to the bit: include/ttm.h)
+        const double delta = band_interval_slope(x_lo, x_hi, y_lo, y_hi) * (tgt - x_lo);
         rr = delta + y_lo;
         const double w = (delta * -0.25) * (y_lo + rr);
         double p = fma(kt[0], w, kt[1]);
@@ -2029,10 +2051,8 @@ __global__ __launch_bounds__(BAND_CT) void k_band_few_roundtrip(const double* __
     const int4 bv = *(const int4*)(bkt + (int64_t)bc * (nb + 1) + 4 * bw);
     __builtin_amdgcn_sched_barrier(0);
     auto interp = [&](double y_lo, double y_hi, double x_lo, double x_hi, double e_lo, double tgt, double& rr, double& ee) {
-        const double dx = fmax(x_hi - x_lo, 1e-300);
-        double rc = __builtin_amdgcn_rcp(dx);
-        rc = fma(fma(-dx, rc, 1.0), rc, rc);
-        const double delta = ((y_hi - y_lo) * rc) * (tgt - x_lo);           // (the abscissae are np.linspace's to the bit: include/ttm.h)
+        // (the abscissae are np.linspace's to the bit: include/ttm.h)
+        const double delta = band_interval_slope(x_lo, x_hi, y_lo, y_hi) * (tgt - x_lo);
         rr = delta + y_lo;
         const double w = (delta * -0.25) * (y_lo + rr);
         double p = fma(kt[0], w, kt[1]);
@@ -3392,10 +3412,11 @@ bool bisect_plans(const ttm_program* p, const double* U, int k0, int k1, const d
 constexpr double BAND_WFRAC = 0.52;                  /* fraction of a table's grid points a window keeps (k_inverse_rt) */
 
 // resident-table images (ttm_band_image.h) of the components [k0, k1) for this table geometry: the plan, or false
-bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, size_t lds_per_cu, int window, int block, int* w0, int* W, int* tab_slot) {
+bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, size_t lds_per_cu, int window, int block, int slopes, int* w0, int* W,
+                int* tab_slot) {
     if (!usable(p, k0, k1) || p->u_p_lag != 2 || k1 - k0 <= TTM_P_FEW_D) return false;
     BandRingPlan pl;
-    if (!band_ring_plan(T, nb, k1 - k0, lds_per_cu, window, block, BAND_WFRAC, &pl)) return false;
+    if (!band_ring_plan(T, nb, k1 - k0, lds_per_cu, window, block, BAND_WFRAC, &pl, slopes)) return false;
     *w0 = pl.w0; *W = pl.W; *tab_slot = pl.tab_slot;
     return true;
 }
@@ -3419,7 +3440,7 @@ static BlockPlan block_plan(int T, int W, int nb, int ncomp, size_t lds_per_cu, 
 int inverse(const ttm_program* p, const double* U, int k0, int k1, const double* Zsoa, int64_t ldz, double* Xsoa, int64_t ldx, int64_t N,
             const double* tab_x, int T, const double* y_affine, const double* tmin, const double* tmax, const int32_t* bkt, int nb, const double* img,
             int img_doubles, int cus, size_t lds_per_cu, int window, int block, int resident, int full_tiles, int zdma, int ring_slots,
-            void* stream, const char** kernel_name) {
+            int slopes, void* stream, const char** kernel_name) {
     if (!usable(p, k0, k1) || T < 64 || T > 4096 || nb + 1 != 1024 || N >= ((int64_t)1 << 28)) return 1;      // (bucket rows copied 16 bytes at a time, 256 units per row)
     if (!vec_ok(bkt) || !y_affine_ok(y_affine)) return 1;
     if (!col_ok(Zsoa, ldz, even_rows(N)) || !col_ok(Xsoa, ldx, even_rows(N))) return 1;
@@ -3445,16 +3466,24 @@ int inverse(const ttm_program* p, const double* U, int k0, int k1, const double*
     const ChunkGrid cg = chunk_grid(N, cus);
     // resident-table images at hand (ttm_inverse_table_build_index wrote them): the ring kernel
     BandRingPlan pl;
-    if (img && vec_ok(img) && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl) &&
-        pl.tab_slot == img_doubles) {                         // (laid out for another plan - options changed in between: not this kernel)
+    bool ring = img && vec_ok(img) && band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl, slopes);
+    // a coefficient vector's images follow the value of band_slopes they were built under: the doubles per image tell the layout
+    // (an image with slopes is larger than any image without under the same window option), so the plan of the other value is tried
+    // too.  The doubles per image are an exact signature only while rt_window stays what it was at the build: an image without
+    // slopes of a window with Weven = 2 Weven' has as many doubles as one with slopes of a window with Weven', so a caller that
+    // changes rt_window AND band_slopes between build and lookup in just that ratio would have its images read in the wrong layout
+    if (ring && pl.tab_slot != img_doubles) ring = band_ring_plan(T, nb, ncomp, lds_per_cu, window, block, BAND_WFRAC, &pl, pl.slopes ? 0 : 1);
+    if (ring && pl.tab_slot == img_doubles) {                 // (laid out for another plan - options changed in between: not this kernel)
         // the cut (as forward()), the cache policy, ZD and the slots of the ring: band_ring_launch, ttm_band_image.h
         const BandRingLaunch rl = band_ring_launch(pl, N, cus, ncomp, lds_per_cu, full_tiles, resident, zdma, ring_slots);
         const BandCut lc = rl.cut;
         const bool pol = rl.pol, zd = rl.zd;
         pl = rl.ring;
+        const bool sl = pl.slopes != 0;
         auto rk = with_bool(pl.G == 4, [&](auto G4) {
             return with_cls<3>(cls, [&](auto C) {
                 constexpr int CL = decltype(C)::value, GG = decltype(G4)::value ? 4 : 0;
+                if (sl) return pol ? k_band_inverse_ring<CL, 2, GG, 1, 0, 1> : k_band_inverse_ring<CL, 2, GG, 0, 0, 1>;   // (never beside ZD: band_ring_launch)
                 return zd ? k_band_inverse_ring<CL, 2, GG, 1, 1> : pol ? k_band_inverse_ring<CL, 2, GG, 1> : k_band_inverse_ring<CL, 2, GG>;
             });
         });

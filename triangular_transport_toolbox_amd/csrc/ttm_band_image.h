@@ -9,6 +9,14 @@
 //   [wl, wh, bucket scale, bucket bias, int32 {entries per bucket at most, 0}, int32 {degenerate, 0} |
 //    xs: the W table entries of the window [w0, w0 + W) + sentinels (+inf) up to Weven | bucket index: nb + 1 uint16, zero padded]
 // exactly what the block prologue of k_band_inverse leaves in a table slot (the same values, the same bits).
+//
+// The SLOPE layout (BandImageSlot::slopes, chosen by band_ring_plan) puts Weven more doubles between xs and the bucket index:
+//   [header | xs: Weven | slopes: Weven | bucket index]
+// slopes[i] = band_interval_slope of the interval BELOW window entry i, (x, y) of table entries w0 + i - 1 and w0 + i - the
+// first window entry takes the table entry in front of the window as its x_lo; 0 where there is no such interval (entry 0
+// of the table, the sentinels).  The slope is a function of the table alone, so the lookup reads it instead of forming it per
+// row (a reciprocal, its Newton step, two differences, a product and two LDS reads): the same operations in the same order,
+// done once by the kernel that builds the table - the same bits.
 #pragma once
 
 #include <math.h>
@@ -24,25 +32,28 @@
 // THE one copy of this geometry: the kernel that writes the images and every kernel that reads them take it from here.
 struct BandImageSlot {
     int Weven, tab_slot;
+    int slopes;                                       // 1: the slope layout
     size_t lds(int slots) const { return ((size_t)2 * Weven + (size_t)slots * tab_slot) * 8; }   // `slots` images next to the {E_i, y_i} pairs of the window
+    int index_at() const { return BAND_RT_HDR + (slopes ? 2 : 1) * Weven; }                      // where the bucket index starts (doubles)
 };
-static inline BandImageSlot band_image_slot(int W, int nb) {
+static inline BandImageSlot band_image_slot(int W, int nb, int slopes = 0) {
     const int Weven = (W + 4 + 1) & ~1;
-    return {Weven, BAND_RT_HDR + Weven + (((nb + 1 + 3) / 4 + 1) & ~1)};
+    return {Weven, BAND_RT_HDR + (slopes ? 2 : 1) * Weven + (((nb + 1 + 3) / 4 + 1) & ~1), slopes ? 1 : 0};
 }
 
 struct BandRingPlan {
     int W, w0, Weven, tab_slot;                       // window [w0, w0 + W) of every table, doubles per image
     int R, G;                                         // ring of R slots, refilled G at a time (G = 0: every component resident, no refill)
     size_t lds;                                       // dynamic LDS of the launch
+    int slopes;                                       // 1: the images carry the interval slopes (BandImageSlot)
 };
 
-// The plan is a function of the table geometry, the number of components and the LDS of a CU alone: the kernel that writes
-// the images and the kernel that reads them compute it separately and agree.  false: no ring kernel for this geometry.
-static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, int window, int block, double wfrac, BandRingPlan* pl) {
+// The plan of ONE layout (band_ring_plan below chooses between the two).  false: no ring kernel for this geometry and layout.
+static inline bool band_ring_plan_layout(int T, int nb, int ncomp, size_t lds_per_cu, int window, int block, double wfrac, int slopes,
+                                         BandRingPlan* pl) {
     if (T < 64 || T > 4096 || nb + 1 != 1024 || ncomp < 1) return false;
     auto fit = [&](int W) {                           // slots that fit next to the {E_i, y_i} pairs of the window
-        const BandImageSlot s = band_image_slot(W, nb);
+        const BandImageSlot s = band_image_slot(W, nb, slopes);
         if (s.lds(1) > lds_per_cu) return 0;
         int B = (int)((lds_per_cu - s.lds(0)) / ((size_t)s.tab_slot * 8));
         if (B > BAND_RING_KMAX) B = BAND_RING_KMAX;
@@ -60,8 +71,8 @@ static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, i
     }
     if (B <= 0) return false;
     pl->W = W; pl->w0 = w0;
-    const BandImageSlot slot = band_image_slot(W, nb);
-    pl->Weven = slot.Weven; pl->tab_slot = slot.tab_slot;
+    const BandImageSlot slot = band_image_slot(W, nb, slopes);
+    pl->Weven = slot.Weven; pl->tab_slot = slot.tab_slot; pl->slopes = slot.slopes;
     if (pl->tab_slot % 2) return false;               // (16-byte units)
     if (ncomp <= B) { pl->R = ncomp; pl->G = 0; }
     else {
@@ -74,12 +85,35 @@ static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, i
     return true;
 }
 
+// option band_slopes (ttm_options.h): -1 auto, 0 off, 1 on wherever the plan allows.  Auto: on (measured: OPTLOG round 16).
+constexpr int BAND_SLOPES_AUTO = 1;
+
+// The plan is a function of the table geometry, the number of components, the LDS of a CU and the options alone: the kernel
+// that writes the images and the kernel that reads them compute it separately and agree.  false: no ring kernel for this geometry.
+// The slope layout makes an image larger by Weven doubles (C5: 786 -> 1310, 14 slots beside the pairs instead of 24), so it is
+// taken only where it leaves the KIND of plan alone:
+//   * a refilled ring stays a legal refilled ring (R >= 3 G: 12 slots at C5, measured no slower than 24 - OPTLOG round 15), or
+//   * every component is resident under both layouts (the window may differ: ten whole tables fit, ten whole tables with
+//     their slopes do not, ten windowed ones do).
+// It is NOT taken where it would turn a map that is fully resident today (G = 0, up to 24 components) into a refilled one, nor
+// where today's layout has no plan: such geometries keep today's image and today's code.
+static inline bool band_ring_plan(int T, int nb, int ncomp, size_t lds_per_cu, int window, int block, double wfrac, BandRingPlan* pl,
+                                  int slopes_option = 0) {
+    if (!band_ring_plan_layout(T, nb, ncomp, lds_per_cu, window, block, wfrac, 0, pl)) return false;
+    if (slopes_option < 0) slopes_option = BAND_SLOPES_AUTO;
+    BandRingPlan with;
+    if (slopes_option > 0 && band_ring_plan_layout(T, nb, ncomp, lds_per_cu, window, block, wfrac, 1, &with) && (with.G == 0) == (pl->G == 0) &&
+        (with.G == 0 || with.tab_slot <= 2048))            // (a refill copies an image as one 1 KB piece per wave of the lookup kernel: 16 waves)
+        *pl = with;
+    return true;
+}
+
 // The plan `pl` with `extra` bytes of LDS behind the {E_i, y_i} pairs (the column buffers of k_band_inverse_ring's ZD = 1)
 // and at most `max_slots` slots (0: as many as fit): the SAME images - window and doubles per image are what the table
 // kernel wrote - in a ring of fewer slots.  A ring without refill keeps every component whatever `max_slots`.  false: the
 // slots left are fewer than the ring needs (every component when there is no refill, else the 3 G of band_ring_plan).
 static inline bool band_ring_plan_with(const BandRingPlan& pl, size_t lds_per_cu, size_t extra, int max_slots, BandRingPlan* out) {
-    const BandImageSlot slot = {pl.Weven, pl.tab_slot};
+    const BandImageSlot slot = {pl.Weven, pl.tab_slot, pl.slopes};
     if (slot.lds(0) + extra > lds_per_cu) return false;
     const int B = (int)((lds_per_cu - extra - slot.lds(0)) / ((size_t)slot.tab_slot * 8));
     *out = pl;
@@ -109,8 +143,9 @@ static inline BandRingLaunch band_ring_launch(const BandRingPlan& pl, int64_t N,
     l.pol = (band_resident_policy(N, l.cut.rows, ncomp, resident) & BAND_POLICY_INVERSE) != 0;
     const int slots = ring_slots > 0 ? ring_slots : 0;
     BandRingPlan with;
-    // Z two columns ahead through LDS: the same images in the slots the two column buffers leave
-    l.zd = band_zdma_policy(N, l.cut, l.pol, band_ring_plan_with(pl, lds_per_cu, (size_t)BAND_ZDMA_LDS_BYTES, slots, &with), zdma);
+    // Z two columns ahead through LDS: the same images in the slots the two column buffers leave - never images with slopes
+    // (they leave the buffers no room at C5, and k_band_inverse_ring has no such instantiation)
+    l.zd = band_zdma_policy(N, l.cut, l.pol, !pl.slopes && band_ring_plan_with(pl, lds_per_cu, (size_t)BAND_ZDMA_LDS_BYTES, slots, &with), zdma);
     l.ring = pl;
     if (l.zd || (slots > 0 && band_ring_plan_with(pl, lds_per_cu, 0, slots, &with))) l.ring = with;
     return l;
@@ -123,11 +158,25 @@ __device__ __forceinline__ void band_bucket_params(double lo, double hi, int nb,
     bias = -lo * scale;
 }
 
+// THE one definition of an interval's slope, interp1d's slope form (TM:4062-4065) with the difference floored (the tie at a
+// flat start: include/ttm.h, THE TIE RULE): what the lookup kernels form per row and what band_image_write stores per interval.
+__device__ __forceinline__ double band_interval_slope(double x_lo, double x_hi, double y_lo, double y_hi) {
+    const double dx = fmax(x_hi - x_lo, 1e-300);
+    double rc = __builtin_amdgcn_rcp(dx);
+    rc = fma(fma(-dx, rc, 1.0), rc, rc);
+    return (y_hi - y_lo) * rc;
+}
+
 // One workgroup writes the image of its component: xs (LDS, the T sorted table entries), bks (LDS, nb + 1 bucket starts as
-// k_table_index computes them), red (LDS, one int, any value).  Every thread of the workgroup calls it.
+// k_table_index computes them), red (LDS, one int, any value).  Every thread of the workgroup calls it.  ys (slope layout
+// only - tab_slot tells): the T abscissae of the table, the values a lookup computes as i * step + y0 (y_last at T - 1) to
+// the bit (include/ttm.h, THE ABSCISSAE: a lookup that passes h_y_affine vouches for exactly that).
 __device__ inline void band_image_write(const double* xs, const int* bks, int* red, int T, int nb, double lo, double hi, int w0, int W,
-                                        int Weven, int tab_slot, double* __restrict__ img) {
+                                        int Weven, int tab_slot, double* __restrict__ img, const double* __restrict__ ys = nullptr) {
     const int tid = threadIdx.x, nt = blockDim.x;
+    const int nbd = ((nb + 1 + 3) / 4 + 1) & ~1;       // doubles of the bucket index (band_image_slot)
+    const bool slopes = tab_slot == BAND_RT_HDR + 2 * Weven + nbd;
+    const int index_at = tab_slot - nbd;
     if (tid == 0) *red = 0;
     __syncthreads();
     // entries per bucket, at most, over the buckets that reach into the window
@@ -152,8 +201,12 @@ __device__ inline void band_image_write(const double* xs, const int* bks, int* r
         ih[0] = per; ih[1] = 0; ih[2] = deg ? 1 : 0; ih[3] = 0;
     }
     for (int i = tid; i < Weven; i += nt) img[BAND_RT_HDR + i] = xw(i);
+    if (slopes)
+        for (int i = tid; i < Weven; i += nt) {
+            const int g = w0 + i;                     // the interval below table entry g
+            img[BAND_RT_HDR + Weven + i] = i < W && g >= 1 ? band_interval_slope(xs[g - 1], xs[g], ys[g - 1], ys[g]) : 0.0;
+        }
     // bucket index: four uint16 per double, zero behind entry nb
-    const int nbd = tab_slot - BAND_RT_HDR - Weven;
     for (int i = tid; i < nbd; i += nt) {
         unsigned long long pk = 0;
         for (int j = 0; j < 4; ++j) {
@@ -161,7 +214,7 @@ __device__ inline void band_image_write(const double* xs, const int* bks, int* r
             const unsigned long long v = q <= nb ? (deg ? (unsigned)(w0 + 1) : (unsigned)bks[q]) & 0xffffu : 0u;
             pk |= v << (16 * j);
         }
-        img[BAND_RT_HDR + Weven + i] = __longlong_as_double((long long)pk);
+        img[index_at + i] = __longlong_as_double((long long)pk);
     }
 }
 #endif

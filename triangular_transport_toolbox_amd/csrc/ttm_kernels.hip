@@ -2033,7 +2033,7 @@ __global__ __launch_bounds__(256) void k_table_index(const double* __restrict__ 
 // (the fused kernel below writes it from what it holds in LDS; this one serves the two-launch path)
 __global__ __launch_bounds__(256) void k_table_image(const double* __restrict__ tab_x, int T, int nb, const double* __restrict__ tmin,
                                                      const double* __restrict__ tmax, const int* __restrict__ bkt, double* __restrict__ img,
-                                                     int w0, int W, int slot) {
+                                                     int w0, int W, int slot, const double* __restrict__ pts) {
     __shared__ double xs[2048];
     __shared__ int bks[1024];
     __shared__ int red;
@@ -2041,7 +2041,7 @@ __global__ __launch_bounds__(256) void k_table_image(const double* __restrict__ 
     for (int i = threadIdx.x; i < T; i += blockDim.x) xs[i] = row[i];
     for (int q = threadIdx.x; q <= nb; q += blockDim.x) bks[q] = bkt[(int64_t)blockIdx.x * (nb + 1) + q];
     __syncthreads();
-    band_image_write(xs, bks, &red, T, nb, tmin[blockIdx.x], tmax[blockIdx.x], w0, W, (W + 4 + 1) & ~1, slot, img + (int64_t)blockIdx.x * slot);
+    band_image_write(xs, bks, &red, T, nb, tmin[blockIdx.x], tmax[blockIdx.x], w0, W, (W + 4 + 1) & ~1, slot, img + (int64_t)blockIdx.x * slot, pts);
 }
 
 // k_table_build + k_table_index as ONE launch, one workgroup per component (blockIdx.x = component k0 + x): the table's T
@@ -2109,7 +2109,7 @@ __device__ __forceinline__ void table_body(const DevProg& P, int k, int krel, in
     // the resident-table image of the component for the banded-map lookup kernel (csrc/ttm_band_image.h)
     if (img) {
         __syncthreads();
-        band_image_write(xs, bks, &bad, T, nb, lo, hi, img_w0, img_W, (img_W + 4 + 1) & ~1, img_slot, img + (int64_t)krel * img_slot);
+        band_image_write(xs, bks, &bad, T, nb, lo, hi, img_w0, img_W, (img_W + 4 + 1) & ~1, img_slot, img + (int64_t)krel * img_slot, pts);
     }
 }
 
@@ -3356,8 +3356,12 @@ static int64_t persistent_grid(int64_t tiles, int wgs) {
 static int band_cus() { return tuning().band_cus > 0 ? tuning().band_cus : device_info().cus; }
 
 // resident-table images of the components [k0, k1) for this table geometry (ttm_band::image_plan with the options' window and block)
+// option band_slopes as the image build and the lookup both take it: ZD = 1 has no kernel for images with slopes, so asking
+// for it (band_zdma = 1) keeps today's images
+static int band_slopes_option() { return tuning().band_zdma > 0 ? 0 : tuning().band_slopes; }
 static bool image_plan(const ttm_program* p, int k0, int k1, int T, int nb, int* w0, int* W, int* slot) {
-    return ttm_band::image_plan(p, k0, k1, T, nb, device_info().lds_per_cu, tuning().rt_window, tuning().rt_block, w0, W, slot);
+    return ttm_band::image_plan(p, k0, k1, T, nb, device_info().lds_per_cu, tuning().rt_window, tuning().rt_block, band_slopes_option(), w0, W,
+                                slot);
 }
 
 static DevProg dev_prog(const ttm_program* p) {
@@ -3971,7 +3975,7 @@ int ttm_inverse_table_build_index(const ttm_program* p, const double* coef, cons
             return set_err(TTM_E_HIP, "ttm_inverse_table_build_index: copy of the flags failed%s");
         if (!rc && img) {
             hipLaunchKernelGGL(k_table_image, dim3(k1 - k0), dim3(256), 0, (hipStream_t)stream, out, (int)T, (int)nb, tmin, tmax, (const int*)bkt, img,
-                               iw0, iW, islot);
+                               iw0, iW, islot, pts);
             rc = check_launch("k_table_image");
         }
         return rc;
@@ -4062,7 +4066,7 @@ int ttm_inverse_table(const ttm_program* p, const double* coef, const double* fo
         const char* name = nullptr;
         if (ttm_band::inverse(p, fold + fold_base_size(p), k0, k1, Zsoa, ldz, Xsoa, ldx, N, tab_x, (int)T, h_y_affine, tmin, tmax, bkt, (int)nb,
                               tn.band_ring != 0 ? img : nullptr, (int)img_doubles, band_cus(), device_info().lds_per_cu, tn.rt_window, tn.rt_block,
-                              tn.band_resident, tn.band_full_tiles, tn.band_zdma, tn.band_ring_slots, stream, &name) == 0)
+                              tn.band_resident, tn.band_full_tiles, tn.band_zdma, tn.band_ring_slots, band_slopes_option(), stream, &name) == 0)
             return check_launch(name);
     }
     // k_inverse_rt sweeps the hot records themselves: not for lag-3 maps (include/ttm.h), and with fewer than four

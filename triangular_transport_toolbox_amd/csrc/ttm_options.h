@@ -32,6 +32,7 @@
     X(band_full_tiles, -1) /* cut of k_band_forward / k_band_inverse_ring launches (csrc/ttm_band_policy.h): 0 N / #CUs rows per workgroup, 1 whole tiles of 4096 rows wherever they give every CU at most one */ \
     X(band_zdma, -1)     /* k_band_inverse_ring requests Z two columns ahead through LDS on full tiles (ZD = 1, beside the resident policy only): 0 off, 1 wherever it fits */ \
     X(band_ring_slots, -1) /* slots of a refilled ring of k_band_inverse_ring: 0 as many as fit, > 0 at most that many (whole groups of 4, 12 at least) */ \
+    X(band_slopes, -1)   /* resident-table images with the slope of every interval, read by k_band_inverse_ring instead of formed per row (csrc/ttm_band_image.h): 0 off, 1 wherever the ring plan allows; images follow the value they were built under */ \
     X(int_dense, -1)     /* 0: integrated maps with dense B sets through the generic kernels instead of csrc/ttm_int.hip */ \
     X(int_xprog, -1)     /* 0: integrated components without their X programs (csrc/ttm_xprog.h: forward map, objective / gradient sums); \
                             2: the root searches through them as well (measured: the weights are 1 % of a bisection - no gain, 5 % slower at C2a) */ \
