@@ -13,6 +13,10 @@ exact(comp, t, ...) evaluates, in mpmath and from those stored doubles alone,
 
 with its first and second derivative in t and the sum of the absolute values of every term that enters the value: it is exact on
 what is stored (no rounding of u, s or the Horner passes), so it is the yardstick of an evaluator's rounding, not of the fit.
+
+group_terms / monotone give the pieces of the same sum one by one with their first and second derivatives and the sums of |terms|
+of each (what tests/test_score_exact.py assembles S, dS/du and m'' / m' from); read_push reads the push records of a banded map
+back and returns the components as the band kernels read them.
 """
 from dataclasses import dataclass, field
 
@@ -66,6 +70,7 @@ class Component:
     err: tuple = (0.0, 0.0)  # self-reported fit errors {value, derivative}
     t_lo: float = 0.0        # host geometry (cm.ugeo): what the builder placed its nodes with
     h: float = 0.0
+    s0: np.ndarray = None    # read_push: the stored local-coordinate offset of every column (None: s from u, as the U-form evaluators)
 
     @property
     def own_linear_slope(self):
@@ -146,6 +151,115 @@ def _group_value(g, x):
     d1 = a1 + e * (b1 - x * b / 2)
     d2 = a2 + e * (b2 - x * b1 + (x * x / 4 - mp.mpf(1) / 2) * b)
     return [v, d1, d2], ma + e * mb, ma1 + e * (mb1 + abs(x) * mb / 2)
+
+
+def horner(coefs, x):
+    """[p, p', p''] of the monomial coefficients `coefs` (doubles) at x, in mpmath (poly's values, without its sums; trailing zero
+    coefficients are skipped)."""
+    x = mp.mpf(x)
+    p = d1 = d2 = mp.mpf(0)
+    for cj in reversed(coefs[:degree(coefs) + 1]):
+        d2 = d2 * x + 2 * d1
+        d1 = d1 * x + p
+        p = p * x + mp.mpf(float(cj))
+    return [p, d1, d2]
+
+
+def mags(coefs, x):
+    """[sum |c_j x^j|, sum |j c_j x^(j-1)|, sum |j (j-1) c_j x^(j-2)|, |sum j (j-1) (j-2) c_j x^(j-3)|] as doubles: the sums of the
+    absolute values of the terms of p, p', p'' (magnitudes: a bound's weights, never a reference value) and the size of p'''."""
+    c = np.asarray(coefs, dtype=float)
+    j = np.arange(len(c), dtype=float)
+    ax, fx = abs(float(x)), float(x)
+    pw = lambda r, b: np.where(j >= r, b ** np.maximum(j - r, 0.0), 0.0)      # noqa: E731
+    return [float(np.sum(np.abs(c) * pw(0, ax))), float(np.sum(np.abs(c) * j * pw(1, ax))), float(np.sum(np.abs(c) * j * (j - 1) * pw(2, ax))),
+            abs(float(np.sum(c * j * (j - 1) * (j - 2) * pw(3, fx))))]
+
+
+def degree(coefs):
+    """Index of the last nonzero coefficient (0 for an all-zero set): the Horner steps that can round."""
+    nz = np.nonzero(np.asarray(coefs))[0]
+    return int(nz[-1]) if len(nz) else 0
+
+
+def group_terms(g, x):
+    """A group f(x) = A(x) + E B(x), E = exp(-x^2/4), at x in full: dict(d=[f, f', f''] in mpmath (_group_value's), mag=[sums of
+    |terms| of f, f', f''] (doubles; the second is the group's derivative magnitude), E, w=[|B|, |B' - x B / 2|,
+    |B'' - x B' + (x^2/4 - 1/2) B|] (doubles: what an error of E is multiplied by in f, f', f'') and deg = (degree of B, of A))."""
+    x = mp.mpf(float(x))
+    a, a1, a2 = horner(g.A, x)
+    b, b1, b2 = horner(g.B, x)
+    e = mp.exp(-x * x / 4)
+    parts = [b, b1 - x * b / 2, b2 - x * b1 + (x * x / 4 - mp.mpf(1) / 2) * b]
+    ma, mb, ef, ax = mags(g.A, x), mags(g.B, x), float(e), abs(float(x))
+    mag = [ma[0] + ef * mb[0], ma[1] + ef * (mb[1] + ax * mb[0] / 2), ma[2] + ef * (mb[2] + ax * mb[1] + (ax * ax / 4 + 0.5) * mb[0])]
+    return dict(d=[a + e * parts[0], a1 + e * parts[1], a2 + e * parts[2]], mag=mag, E=e, w=[abs(float(v)) for v in parts],
+                deg=(degree(g.B), degree(g.A)))
+
+
+def monotone(comp, t, col=None):
+    """The monotone part m(t) = own(t) + P_col(s) of a component at t (a double), from the stored doubles: dict(d=[m, m', m''] in
+    mpmath, mag=[sums of |terms| of m, m', m''] (doubles), u, s, col, dP=[|P'|, |P''|, |P'''|] in the local coordinate (doubles, 0
+    without a spline), own=group_terms of the own group or None).  col: the spline column to take (None: column_of's); a
+    component read from the push records (s0 set) takes its local coordinate as the band kernels do, s = t sp_ds + s0[col] with
+    s0 the stored double."""
+    t = float(t)
+    d, mag = [mp.mpf(0)] * 3, [0.0] * 3
+    own = None
+    if comp.own is not None:
+        own = group_terms(comp.own, t)
+        d, mag = list(own['d']), list(own['mag'])
+    out = dict(u=None, s=None, col=None, dP=[0.0] * 3, own=own)
+    if comp.nI > 0:
+        c_own, u, _ = column_of(comp, t)
+        col = c_own if col is None else int(col)
+        if comp.s0 is None:
+            s = 2 * (u - (col - 1)) - 1
+        else:
+            s = mp.mpf(t) * mp.mpf(comp.sp_ds) + mp.mpf(float(comp.s0[col]))
+        p, p1, p2 = horner(comp.table[col], s)
+        pm = mags(comp.table[col], s)
+        ds = mp.mpf(comp.sp_ds)
+        d = [d[0] + p, d[1] + p1 * ds, d[2] + p2 * ds * ds]
+        mag = [mag[0] + pm[0], mag[1] + pm[1] * comp.sp_ds, mag[2] + pm[2] * comp.sp_ds * comp.sp_ds]
+        out.update(u=u, s=s, col=col, dP=[abs(float(p1)), abs(float(p2)), pm[3]])
+    out.update(d=d, mag=mag)
+    return out
+
+
+def read_push(tm, comps):
+    """The push records of a banded map (include/ttm.h "push records"; csrc/ttm_uform.h: uform_scatter_push_records) read back from
+    the fold buffer: (P [D + lag, stride], push) - push[k] is component k as the band kernels read it: c0 = record k's chain start
+    [0] (the component's constants and its groups' A[0], summed by the builder), every group's B[0..DB] and A[1..DA] from its
+    block (A[0] = 0: it is in the chain start), the own term's slope from [7], the spline table with the stored local-coordinate
+    offsets s0 (padding slot 12 of the columns).  Coefficients beyond a class's degrees are not in a record: they read 0 here."""
+    import dataclasses
+    cm = tm._cm
+    lag, ps, cls = int(cm.u_p_lag), int(cm.u_p_stride), int(cm.u_h_cls)
+    assert lag > 0, 'the map has no push records'
+    U, _ = u_section(tm)
+    D = cm.D
+    P = np.array(U[int(cm.u_p_off):int(cm.u_p_off) + (D + lag) * ps]).reshape(D + lag, ps)
+    DB, DA = termtable.H_DB[cls], termtable.H_DA[cls]
+    GP = DB + 1 + DA
+    push = []
+    for k, c in enumerate(comps):
+        groups = []
+        for g in c.groups:
+            lg = c.kc - g.var
+            assert 1 <= lg <= lag, 'a group outside the band'
+            blk = P[k - lg + lag, termtable.P_HDR + (lg - 1) * GP:termtable.P_HDR + lg * GP]
+            B, A = np.zeros(U_GHALF), np.zeros(U_GHALF)
+            B[:DB + 1] = blk[:DB + 1]
+            A[1:DA + 1] = blk[DB + 1:]
+            groups.append(Group(g.var, g.flags, B, A))
+        own = None
+        if c.own is not None:
+            A = np.zeros(U_GHALF)
+            A[1] = P[k + lag, 7]
+            own = Group(c.kc, UGF_POLY | (1 << 24), np.zeros(U_GHALF), A)
+        push.append(dataclasses.replace(c, c0=float(P[k, 0]), groups=groups, own=own, s0=c.padding[:, 0].copy()))
+    return P, push
 
 
 def exact(comp, t, col=None, others=0.0):
